@@ -8,19 +8,29 @@ pass of the hot path (analysis -> phase processing -> resynthesis + overlap-add,
 pv_process) over that batch, with the input resident in HBM.  Channels shard across
 ranks with no data-path collective (weak scaling).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--channels C] [--no-cpu]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--channels C] [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N bench.py --gpus N ...       (one process per GPU, RCCL)
 
 `--gpus N` without a launcher starts the N rank processes itself (launch_ranks); with one
 (WORLD_SIZE set) it must equal WORLD_SIZE.  PV_DIST_BACKEND=gloo runs the same N-rank path
 over gloo (collectives on host tensors) — how the one-GPU box rehearses it.
 
-The synthetic channels are generated once on the host and uploaded; after the timed
-steps the whole output is checked for finiteness and 16 channels spread over the batch
-(first and last included) are compared with the CPU oracle (`rms_vs_oracle`, bar 1e-5
-RMS per sample), and the CPU baseline is timed on a bounded prefix of the same channels.
+The synthetic channels are generated once on the host (seeded per channel: the same
+arguments give the same inputs in every run) and uploaded.  A plain run sets up, warms up,
+times the K steps and prints the line; the figures that come out of the timed steps
+themselves (ms_per_step, the per-kernel event times and the roofline computed from them)
+are on it.  `--dump-outputs DIR` then writes what the last timed step handed its caller as
+DIR/<name>.npy (float32; an output larger than the budget as a fixed, seeded sample of its
+elements — DUMP_BYTES in all).
 
-Rank 0 prints ONE JSON line (metric, value, roofline{...}, rms_vs_oracle{...},
+`--full` adds what takes runs of its own: the whole output is checked for finiteness and 16
+channels spread over the batch (first and last included) are compared with the CPU oracle
+(`rms_vs_oracle`, bar 1e-5 RMS per sample), and the CPU baseline is timed on a bounded
+prefix of the same channels (`--no-check` / `--no-cpu` drop either); the real-time workload
+adds its direct-launch comparison and the kernel's device time.  Without it those fields
+are null.
+
+Rank 0 prints ONE JSON line (metric, value, ms_per_step, roofline{...}, rms_vs_oracle{...},
 cpu_baseline{...}, ...).
 """
 from __future__ import annotations
@@ -156,6 +166,35 @@ def cpu_baseline(x, N, hop_div, effect, scale, target_s=10.0, single=False, comp
                       f"{host}", "note": note}
 
 
+DUMP_BYTES = 48 << 20  # --dump-outputs: float32 bytes written in all (shared by the arrays)
+DUMP_SEED = 20240
+
+
+def dump_sample(t, max_elems, seed=DUMP_SEED):
+    """What --dump-outputs stores of a torch tensor (or a view of one): the whole array when
+    it has at most max_elems elements, else the elements at max_elems flat indices (C order
+    over t.shape) drawn with a fixed seed and sorted — the same places in every run and
+    every build, whatever the values.  -> float32 ndarray"""
+    import torch
+    numel = int(t.numel())
+    if numel <= max_elems:
+        return t.detach().to("cpu", torch.float32).contiguous().numpy()
+    flat = np.sort(np.random.default_rng(seed).integers(0, numel, max_elems, dtype=np.int64))
+    idx = tuple(torch.from_numpy(np.ascontiguousarray(i)).to(t.device) for i in np.unravel_index(flat, tuple(t.shape)))
+    return t.detach()[idx].to("cpu", torch.float32).numpy()
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: {name: tensor or ndarray} -> path/<name>.npy, float32, DUMP_BYTES in
+    all (an equal share of it per array)."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // 4 // max(1, len(arrays))
+    for name, a in arrays.items():
+        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+        np.save(os.path.join(path, f"{name}.npy"), dump_sample(t, share))
+
+
 def check_channels(C, k=16):
     """k channel indices spread over the batch, first and last included."""
     return sorted(set(int(round(v)) for v in np.linspace(0, C - 1, min(k, C))))
@@ -182,15 +221,22 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None,
                     help="timed steps (default 10; 200 for the 50-us c2 step, 2000 callbacks for rt)")
-    ap.add_argument("--warmup", type=int, default=None, help="untimed steps (default 3; 20 for c2)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed steps (default 3; 20 for c2, 50 for rt)")
     ap.add_argument("--channels", type=int, default=1024, help="channels per GPU")
     ap.add_argument("--seconds", type=float, default=10.0)
     ap.add_argument("--prof-every", type=int, default=None,
                     help="per-kernel hipEvents on every k-th timed step (default 1; a "
                          "single-launch step is timed as one block instead)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the timed CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes runs of its own: the oracle check of the timed batch, the "
+                         "timed CPU baseline, and for rt the direct-launch comparison and the "
+                         "kernel's device time (a plain run reports null for them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step handed its caller as "
+                         "DIR/<name>.npy (float32; a fixed seeded sample of a large output)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the timed CPU baseline")
     ap.add_argument("--no-check", action="store_true",
-                    help="skip the oracle check of the timed batch (profiling passes only)")
+                    help="with --full: skip the oracle check of the timed batch (profiling passes only)")
     ap.add_argument("--traffic", default=os.path.join(ROOT, "profiles", "traffic.json"))
     ap.add_argument("--write-spec", action="store_true",
                     help="hand the spectrum rows back to the caller (by default STANDARD runs do not: "
@@ -219,9 +265,11 @@ def main():
         return launch_ranks(args.gpus)
     # a c2 step is ~50 us: 10 steps would time the barrier/synchronise bracket, not the path
     if args.steps is None:
-        args.steps = 200 if args.workload == "c2" else 10
+        args.steps = {"c2": 200, "rt": 2000}.get(args.workload, 10)
     if args.warmup is None:
-        args.warmup = 20 if args.workload == "c2" else 3
+        args.warmup = {"c2": 20, "rt": 50}.get(args.workload, 3)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.workload == "rt":
         return bench_rt(args)
 
@@ -407,9 +455,18 @@ def main():
         ceiling = None
     kernels = {k: {"avg_ms": v[0] / max(v[1], 1), "launches": v[1]} for k, v in prof.items()}
 
+    # what the last timed step handed its caller: the output samples, and the spectrum rows
+    # (their bins only: the slots that pad a row to its stride are never written) when it
+    # asked for them.  Rank 0's shard.
+    if args.dump_outputs and rank == 0:
+        arrays = {"out": out}
+        if spec is not None:
+            arrays["spec"] = spec[..., :pv.spec_bins, :]
+        dump_outputs(args.dump_outputs, arrays)
+
     # parity of the timed batch: every sample finite, sampled channels vs the oracle
     check = None
-    if not args.no_check:
+    if args.full and not args.no_check:
         idx = check_channels(C)
         finite = bool(torch.isfinite(out).all().item())
         check = oracle_check(x_host, out[idx].cpu().numpy(), idx, N, hop_div, ord(effect), scale,
@@ -432,7 +489,7 @@ def main():
     cpu = None
     # the CPU baseline is a rank-0, N = 1 figure (the contract's cpu_baseline): an N-rank run
     # reports null rather than time the host while the other ranks wait
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         try:
             cpu = cpu_baseline(x_host, N, hop_div, ord(effect), scale, single=(C == 1), compat=compat)
         except Exception as e:  # reported, never fatal for the GPU number
@@ -444,6 +501,7 @@ def main():
             "metric": METRIC, "value": value, "unit": "frames/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+            "full": bool(args.full),
             "data": "synthetic (3 sines U[55,4000] Hz a=0.1 + U(+-1e-3) noise, seed 20240+ch)",
             "config": {"workload": wl_desc,
                        "channels_per_gpu": C, "frames_per_channel": frames, "N": N, "hop": hop_a,
@@ -617,8 +675,9 @@ def bench_rt(args):
     """BASELINE configs[4]: real-time ring-buffer mode, 256 channels, N=256, hop=64
     (64-sample callbacks at 44.1 kHz: 1.451 ms deadline), PV_STANDARD pitch shift 1.5,
     one hipGraph replay per callback (BASELINE config 5's form; the graph's one kernel node
-    reads / writes the pinned host buffers in place).  The same callbacks are then timed with
-    a direct launch per callback (`alt_direct_launch`: measured faster on ROCm 7.2).  A step
+    reads / writes the pinned host buffers in place).  With --full the same callbacks are then
+    timed with a direct launch per callback (`alt_direct_launch`: measured faster on ROCm 7.2)
+    and the kernel's device time gives `kernel_us` and the roofline.  A step
     = one synchronous callback; latency percentiles are host wall-clock per
     callback (what an RtAudio thread waits for)."""
     import torch
@@ -630,8 +689,7 @@ def bench_rt(args):
     C, N, hop_div, scale = args.channels if args.channels != 1024 else 256, 256, 4, 1.5
     rt = RealTimeVocoder(N, PITCH_SHIFT, scale, hop_div, channels=C, device=local)
     hop = rt.hopSize
-    steps = args.steps if args.steps != 10 else 2000
-    warm = max(args.warmup, 50)
+    steps, warm = args.steps, args.warmup
     blocks = synth_channels_np(C, hop * 64, 20240, cpu_share()[0]).reshape(C, 64, hop)
 
     def run_callbacks(v):
@@ -650,36 +708,43 @@ def bench_rt(args):
     prev = os.environ.pop("PV_RT_LAUNCH", None)
     rt.capture(1)                                  # hipGraph replay per callback (config 5)
     lat, dt = run_callbacks(rt)
-    os.environ["PV_RT_LAUNCH"] = "direct"          # the same callbacks, one launch each
-    alt = RealTimeVocoder(N, PITCH_SHIFT, scale, hop_div, channels=C, device=local)
-    alt.capture(1)
-    lat_d, dt_d = run_callbacks(alt)
-    alt.close()
+    if args.dump_outputs:  # what the last timed callback handed back (host_out, in place)
+        dump_outputs(args.dump_outputs, {"out": rt.host_out})
+    deadline_us = hop / SR * 1e6
+    alt_line = k_us = rt_roof = None
+    if args.full:
+        os.environ["PV_RT_LAUNCH"] = "direct"          # the same callbacks, one launch each
+        alt = RealTimeVocoder(N, PITCH_SHIFT, scale, hop_div, channels=C, device=local)
+        alt.capture(1)
+        lat_d, dt_d = run_callbacks(alt)
+        alt.close()
+        alt_line = {"value": C * steps / dt_d, "p50_us": float(np.percentile(lat_d, 50)),
+                    "p99_us": float(np.percentile(lat_d, 99)), "max_us": float(lat_d.max())}
     if prev is None:
         os.environ.pop("PV_RT_LAUNCH", None)
     else:
         os.environ["PV_RT_LAUNCH"] = prev
-    # device time of the per-callback kernel alone (events on the push stream)
-    x = torch.from_numpy(blocks[:, 0].copy()).cuda()
-    out = torch.empty((C, rt.outHopSize), device="cuda")
-    s = torch.cuda.current_stream()
-    for _ in range(20):
-        rt.push(x, out=out)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(s)
-    for _ in range(200):
-        rt.push(x, out=out)
-    e1.record(s)
-    torch.cuda.synchronize()
-    k_us = e0.elapsed_time(e1) / 200 * 1e3
-    deadline_us = hop / SR * 1e6
-    frame_bytes = 4 * hop + 4 * rt.outHopSize  # SURVEY.md §8(d) fused-mode bytes per frame
-    rt_roof = roofline("rt", k_us * 1e-3, "rt", N, hop, rt.outHopSize, N // 2 + 1, C, False, None)
-    assert abs(rt_roof["alg_bytes_per_launch"] - C * frame_bytes) < 1e-6
-    # one callback of 256 frames is ~7 us of device time, mostly launch and dependent latency
-    rt_roof["bound"] = "latency"
-    rt_roof["latency_note"] = ("a callback's kernel moves 256 frames x 512 B: HBM and VALU both idle; "
-                               "the host round trip per callback (latency_us) is what the deadline sees")
+    if args.full:
+        # device time of the per-callback kernel alone (events on the push stream)
+        x = torch.from_numpy(blocks[:, 0].copy()).cuda()
+        out = torch.empty((C, rt.outHopSize), device="cuda")
+        s = torch.cuda.current_stream()
+        for _ in range(20):
+            rt.push(x, out=out)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(s)
+        for _ in range(200):
+            rt.push(x, out=out)
+        e1.record(s)
+        torch.cuda.synchronize()
+        k_us = e0.elapsed_time(e1) / 200 * 1e3
+        frame_bytes = 4 * hop + 4 * rt.outHopSize  # SURVEY.md §8(d) fused-mode bytes per frame
+        rt_roof = roofline("rt", k_us * 1e-3, "rt", N, hop, rt.outHopSize, N // 2 + 1, C, False, None)
+        assert abs(rt_roof["alg_bytes_per_launch"] - C * frame_bytes) < 1e-6
+        # one callback of 256 frames is ~7 us of device time, mostly launch and dependent latency
+        rt_roof["bound"] = "latency"
+        rt_roof["latency_note"] = ("a callback's kernel moves 256 frames x 512 B: HBM and VALU both idle; "
+                                   "the host round trip per callback (latency_us) is what the deadline sees")
     line = {
         "metric": METRIC + " [real-time mode]", "value": C * steps / dt, "unit": "frames/s",
         "n_gpus": 1, "steps": steps, "warmup": warm, "ms_per_step": dt / steps * 1e3,
@@ -692,8 +757,7 @@ def bench_rt(args):
                        "max": float(lat.max()), "deadline": deadline_us,
                        "missed": int(np.sum(lat > deadline_us))},
         "kernel_us": k_us,
-        "alt_direct_launch": {"value": C * steps / dt_d, "p50_us": float(np.percentile(lat_d, 50)),
-                              "p99_us": float(np.percentile(lat_d, 99)), "max_us": float(lat_d.max())},
+        "alt_direct_launch": alt_line,
         "roofline": rt_roof,
         "world_size_env": world,
     }

@@ -24,16 +24,16 @@ for s in $STEPS; do
   case $s in
     probe3) run valu_probe3 300 scripts/valu_probe3 ;;
     tests) run pytest_gpu 700 python -u -m pytest tests -m gpu -x -q -rf --timeout 120 --timeout-method thread ${PYTEST_ARGS:-}; tail -3 gpurun_out/pytest_gpu.log ;;
-    c3) run bench_c3 400 python bench.py ;;
-    c3q) run bench_c3 300 python bench.py --no-cpu ;;
-    c2) run bench_c2 300 python bench.py --workload c2 ;;
-    c4) run bench_c4 300 python bench.py --workload c4 --no-cpu ;;
-    compat) run bench_compat 300 python bench.py --workload compat ;;
-    rt) run bench_rt 300 python bench.py --workload rt ;;
-    prof) prof prof 400 --steps 40 --warmup 3 --no-cpu ;;
-    prof_c4) prof prof_c4 400 --workload c4 --steps 40 --warmup 3 --no-cpu ;;
-    prof_compat) prof prof_compat 400 --workload compat --steps 20 --warmup 3 --no-cpu ;;
-    prof_c2) prof prof_c2 400 --workload c2 --no-cpu ;;
+    c3) run bench_c3 400 python bench.py --full ;;
+    c3q) run bench_c3 300 python bench.py --full --no-cpu ;;
+    c2) run bench_c2 300 python bench.py --full --workload c2 ;;
+    c4) run bench_c4 300 python bench.py --full --workload c4 --no-cpu ;;
+    compat) run bench_compat 300 python bench.py --full --workload compat ;;
+    rt) run bench_rt 300 python bench.py --full --workload rt ;;
+    prof) prof prof 400 --full --steps 40 --warmup 3 --no-cpu ;;
+    prof_c4) prof prof_c4 400 --full --workload c4 --steps 40 --warmup 3 --no-cpu ;;
+    prof_compat) prof prof_compat 400 --full --workload compat --steps 20 --warmup 3 --no-cpu ;;
+    prof_c2) prof prof_c2 400 --full --workload c2 --no-cpu ;;
     traffic_c3|traffic_c4|traffic_c2)
       w=${s#traffic_}; rm -rf gpurun_out/pmc
       args="--calib"; [ $w = c4 ] && args="--calib --N 2048 --effect p --scale 1.5"

@@ -45,6 +45,25 @@ def test_check_channels_spread():
     assert bench.check_channels(5) == [0, 1, 2, 3, 4]
 
 
+def test_dump_sample_is_fixed_and_bounded(tmp_path):
+    """--dump-outputs: a small array whole, a large one (or a view of one) as the same
+    seeded places in every run; float32 files within the budget."""
+    import torch
+    a = torch.arange(5 * 7 * 6, dtype=torch.float64).reshape(5, 7, 6)
+    whole = bench.dump_sample(a, 1000)
+    assert whole.dtype == np.float32 and np.array_equal(whole, a.numpy())
+    view = a[..., :4]                                   # rows without their padding slots
+    s1, s2 = bench.dump_sample(view, 50), bench.dump_sample(view, 50)
+    assert s1.shape == (50,) and s1.dtype == np.float32 and np.array_equal(s1, s2)
+    flat = np.sort(np.random.default_rng(bench.DUMP_SEED).integers(0, view.numel(), 50))
+    assert np.array_equal(s1, view.contiguous().numpy().reshape(-1)[flat])
+    assert (s1 % 6 < 4).all()                           # never a padding slot
+    bench.dump_outputs(str(tmp_path / "d"), {"out": a, "host": np.ones((2, 3), np.float32)})
+    assert np.array_equal(np.load(tmp_path / "d" / "out.npy"), a.numpy().astype(np.float32))
+    assert np.load(tmp_path / "d" / "host.npy").shape == (2, 3)
+    assert bench.DUMP_BYTES <= 64 << 20
+
+
 def test_oracle_check_detects_error():
     import pvref
     x = bench.synth_channels_np(3, 8192, 20240)

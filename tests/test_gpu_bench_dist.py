@@ -18,7 +18,7 @@ def test_bench_two_ranks_on_one_gpu(cuda):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--channels", "8",
-                        "--seconds", "1", "--steps", "3", "--warmup", "1", "--no-cpu"],
+                        "--seconds", "1", "--steps", "3", "--warmup", "1", "--full", "--no-cpu"],
                        env=env, capture_output=True, text=True, timeout=110)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -41,7 +41,7 @@ def test_bench_two_ranks_config4(cuda):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "c4",
-                        "--channels", "8", "--seconds", "1", "--steps", "3", "--warmup", "1", "--no-cpu"],
+                        "--channels", "8", "--seconds", "1", "--steps", "3", "--warmup", "1", "--full", "--no-cpu"],
                        env=env, capture_output=True, text=True, timeout=110)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -52,6 +52,40 @@ def test_bench_two_ranks_config4(cuda):
     assert d["tables_broadcast"]["bytes"] > 0
     chk = d["rms_vs_oracle"]
     assert chk["pass"] and chk["ranks"] == 2 and chk["all_finite"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_steps_and_dumps_outputs(cuda, tmp_path):
+    """A plain run (no --full): the asked number of timed steps, ms_per_step, no oracle check
+    and no CPU baseline; --dump-outputs leaves the last step's output as float32, and it is
+    what the library computes for the same seeded input."""
+    import numpy as np
+    import torch
+
+    import bench
+    from pvamd import STANDARD, TIME_SHIFT, PhaseVocoder
+    from pvamd._lib import PV_SPEC_PACKED
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--channels", "3",
+                        "--seconds", "0.5", "--steps", "4", "--warmup", "1", "--dump-outputs", str(tmp_path / "d")],
+                       env=env, capture_output=True, text=True, timeout=110)
+    assert p.returncode == 0, p.stderr[-3000:]
+    d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["full"] is False
+    assert d["rms_vs_oracle"] is None and d["cpu_baseline"] is None
+    assert d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    frames = d["config"]["channels_per_gpu"] * d["config"]["frames_per_channel"] * d["steps"]
+    assert abs(d["value"] * d["ms_per_step"] * d["steps"] * 1e-3 - frames) <= 1e-6 * frames
+    assert sorted(os.listdir(tmp_path / "d")) == ["out.npy"]
+    got = np.load(tmp_path / "d" / "out.npy")
+    n = int(round(0.5 * bench.SR))
+    x = torch.from_numpy(bench.synth_channels_np(3, n, 20240)).to(cuda)
+    pv = PhaseVocoder(1024, TIME_SHIFT, 0.5, 4, mode=STANDARD, max_channels=3,
+                      max_frames=bench.pv_frames(n, 256), spec_layout=PV_SPEC_PACKED)
+    out, _ = pv.process(x, spectrum=False)
+    assert got.dtype == np.float32 and np.array_equal(got, out.cpu().numpy())
 
 
 def test_bench_rejects_gpus_world_size_mismatch():
@@ -77,7 +111,7 @@ def test_bench_under_torchrun_one_rank_rccl(cuda):
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                         "--master-addr", "127.0.0.1", "--master-port", str(port),
                         os.path.join(ROOT, "bench.py"), "--gpus", "1", "--channels", "8", "--seconds", "1",
-                        "--steps", "3", "--warmup", "1", "--no-cpu"],
+                        "--steps", "3", "--warmup", "1", "--full", "--no-cpu"],
                        env=env, capture_output=True, text=True, timeout=110)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
