@@ -73,7 +73,7 @@ extern "C" {
                              5: pv_config.tables_external, pv_process(spec = NULL) on the
                                 single launch (later additions are functions only, no
                                 struct change: pv_sources_sha, pv_reserve_spectrum,
-                                pv_segment_*) */
+                                pv_segment_*, pv_set_phase_lock / pv_get_phase_lock) */
 
 typedef struct pv_handle pv_handle;
 
@@ -252,12 +252,30 @@ pv_status pv_segment_resynthesis(pv_handle* h, const pv_float2* spec, long long 
  * output is the same bits as with a spectrum buffer. */
 /* allocate (once, zeroed) the handle's own spectrum rows that pv_process(spec = NULL) uses
  * on the split path, so that such calls can then be captured into a graph; thread-safe; a
- * no-op for a single-launch handle.  Not capturable itself (it allocates). */
+ * no-op for a single-launch handle (unless phase locking is on).  Not capturable itself (it
+ * allocates). */
 pv_status pv_reserve_spectrum(pv_handle* h);
 
 pv_status pv_process(pv_handle* h, const float* x, long long ldx, long long n_samples,
                      int channels, int frames, pv_float2* spec, long long ld_spec, float* out,
                      long long ldo, void* stream);
+
+/* Identity phase locking of the STANDARD time stretch (Laroche & Dolson).
+ * 0 (default): every bin's output phase is propagated on its own.  1: in every frame a bin is
+ * a peak if its magnitude is strictly above those of its neighbours at distance 1 and 2 that
+ * lie in [0, N/2]; every bin takes the output-minus-analysis phase of the nearest peak (the
+ * lower one on a tie; its own if the frame has no peak) and keeps its analysis phase relation
+ * to that peak, so the bins of one partial stay coherent.  The analysis, the spectrum rows and
+ * the unwrap decisions are unchanged.  With locking on, pv_resynthesis, pv_process and
+ * pv_segment_resynthesis run the locked synthesis kernel; a single-launch handle takes the
+ * split path (pv_info.single_launch reads 0, and pv_process(spec = NULL) then uses the
+ * handle's own rows: pv_reserve_spectrum), and goes back to the single launch when locking
+ * is turned off.
+ * STANDARD + PV_TIME_SHIFT handles; otherwise PV_ERR_UNSUPPORTED.  Other values: PV_ERR_ARG.
+ * A setup call (not capturable), ordered like the handle's compute calls: it takes effect
+ * for the calls enqueued after it.  pv_rt and the harmoniser have no such switch. */
+pv_status pv_set_phase_lock(pv_handle* h, int lock);
+int pv_get_phase_lock(const pv_handle* h);
 
 /* ---------------------------------------------------------------- real-time mode
  * A pv_rt streams `channels` mono channels through the STANDARD pipeline one callback at a

@@ -38,10 +38,10 @@ pv_status fail(pv_status s, const std::string& msg) {
     } while (0)
 
 constexpr double kPi = 3.14159265358979323846;
-constexpr int kNumKernels = 8;
+constexpr int kNumKernels = 9;
 const char* kKernelNames[kNumKernels] = {"analysis", "runsum", "carry", "synthesis",
-                                         "seam", "compat_analysis", "rt", "fused"};
-enum { KA = 0, KRS = 1, KC = 2, KS = 3, KSEAM = 4, KCA = 5, KRT = 6, KF = 7 };
+                                         "seam", "compat_analysis", "rt", "fused", "synthesis_locked"};
+enum { KA = 0, KRS = 1, KC = 2, KS = 3, KSEAM = 4, KCA = 5, KRT = 6, KF = 7, KSL = 8 };
 
 bool is_pow2(long long v) { return v > 0 && (v & (v - 1)) == 0; }
 
@@ -148,6 +148,7 @@ struct pv_handle {
     int tables_ready = 1;  // 0: pv_config.tables_external until pv_import_tables
     int mode = 0, effect = 0, pitch = 0, aligned_hop = 1, nan_faithful = 0;
     int packed = 0;  // PV_SPEC_PACKED rows (STANDARD)
+    int phase_lock = 0;  // pv_set_phase_lock: identity phase locking (k_synthesis_locked)
     float scale = 1.0f, rho = 1.0f, inv_q = 1.0f;
     unsigned long long p_mod = 0, q = 1;
     int q_pow2 = 1;
@@ -414,7 +415,10 @@ pv_status do_resynthesis(pv_handle* h, const pv_float2* spec, long long ld_spec,
     p.src_hi = h->src_hi;
     p.t_off = seg ? seg->t_off : 0u;
     const int smode = (h->mode == PV_MODE_REF_COMPAT) ? 1 : (h->pitch ? 2 : 0);
-    PV_LAUNCH(h, KS, s, pv::launch_synthesis(h->L_syn, smode, C, p, s));
+    if (h->phase_lock)  // (STANDARD + PV_TIME_SHIFT: pv_set_phase_lock)
+        PV_LAUNCH(h, KSL, s, pv::launch_synthesis_locked(h->L_syn, C, p, s));
+    else
+        PV_LAUNCH(h, KS, s, pv::launch_synthesis(h->L_syn, smode, C, p, s));
     const int nwg = (nruns + 3) / 4;
     if (nwg > 1 || ola_in != nullptr) {
         pv::SeamParams sm{};
@@ -570,8 +574,9 @@ pv_status pv_get_info(const pv_handle* h, pv_info* info) {
     info->mode = h->mode;
     info->effect = h->effect;
     info->scale = h->scale;
-    info->single_launch = h->F_fused > 0 ? 1 : 0;
-    info->single_launch_frames = h->F_fused;
+    // (phase locking runs on the split path: pv_set_phase_lock)
+    info->single_launch = (h->F_fused > 0 && !h->phase_lock) ? 1 : 0;
+    info->single_launch_frames = info->single_launch ? h->F_fused : 0;
     info->lane_constants = h->k_lane;
     info->spec_layout = h->packed ? PV_SPEC_PACKED : PV_SPEC_NATURAL;
     return PV_OK;
@@ -1020,9 +1025,22 @@ static pv_status reserve_spec_own(pv_handle* h) {
 pv_status pv_reserve_spectrum(pv_handle* h) {
     if (!h) return fail(PV_ERR_ARG, "null handle");
     DeviceGuard g(h->cfg.device);
-    if (h->F_fused > 0) return PV_OK;  // the single launch keeps a spec = NULL spectrum on chip
+    // the single launch keeps a spec = NULL spectrum on chip (with phase locking on, the
+    // handle's calls take the split path)
+    if (h->F_fused > 0 && !h->phase_lock) return PV_OK;
     return reserve_spec_own(h);
 }
+
+pv_status pv_set_phase_lock(pv_handle* h, int lock) {
+    if (!h) return fail(PV_ERR_ARG, "null handle");
+    if (lock != 0 && lock != 1) return fail(PV_ERR_ARG, "pv_set_phase_lock: lock must be 0 or 1");
+    if (h->mode != PV_MODE_STANDARD || h->effect != PV_TIME_SHIFT)
+        return fail(PV_ERR_UNSUPPORTED, "pv_set_phase_lock: STANDARD time-stretch handles only");
+    h->phase_lock = lock;
+    return PV_OK;
+}
+
+int pv_get_phase_lock(const pv_handle* h) { return h ? h->phase_lock : 0; }
 
 pv_status pv_process(pv_handle* h, const float* x, long long ldx, long long n_samples,
                      int channels, int frames, pv_float2* spec, long long ld_spec, float* out,
@@ -1032,7 +1050,8 @@ pv_status pv_process(pv_handle* h, const float* x, long long ldx, long long n_sa
     DeviceGuard g(h->cfg.device);
     ProfCall pc_(h);
     hipStream_t s = (hipStream_t)stream;
-    if (h->F_fused > 0) return do_fused(h, x, ldx, n_samples, channels, frames, spec, ld_spec, out, ldo, s);
+    if (h->F_fused > 0 && !h->phase_lock)
+        return do_fused(h, x, ldx, n_samples, channels, frames, spec, ld_spec, out, ldo, s);
     // spec == NULL: the rows go through the handle's own buffer, and bins no output bin reads
     // (pitch > 1) are not analysed
     int src_hi = -1;

@@ -4,6 +4,7 @@
 // inverse FFT).
 #pragma once
 #include "pv_device.hpp"
+#include "pv_lock.hpp"
 
 
 namespace pv {
@@ -226,7 +227,8 @@ struct SynLds {
 // at most one source per bin — ratio >= 1 — fixed at compile time) (unwrap state M,
 // phprev updated; add_decision = false for a run's first frame, whose decision the carry
 // already holds), MODE 1 REF_COMPAT (kernel.cu:121-129 y-bug), MODE 5: sv is the output
-// spectrum Y itself (k_fused MODE 4).  tq = (t + 1) mod q.
+// spectrum Y itself (k_fused MODE 4), MODE 6 (kModeLocked): MODE 0 with identity phase
+// locking (pv_lock.hpp).  tq = (t + 1) mod q.
 // Result: STORE_LAST: time samples in tile (natural order, padded); else the inverse
 // FFT's last-pass registers z (point lane + 64 last_slot(idx)).
 // QPOW2: the output-phase denominator q is a power of two <= 2^24 (compile-time path);
@@ -298,6 +300,10 @@ __device__ __forceinline__ void synth_frame(const float2 (&sv)[Geo<L>::E + 1], b
         } else {
             PV_FOR_BINS(E, lane, { ekv[i] = lds_ld(&ekl[k]); jkv[i] = lds_ld(&jkl[k]); })
         }
+        // locked (kModeLocked): phc is theta = phi_s - phi in revolutions, the same propagation
+        // with rho / 2 pi - 1 / 2 pi in place of rho / 2 pi (lock_offsets, pv_lock.hpp)
+        static_assert(!(MODE == kModeLocked && Q1), "the locked synthesis has no Q1 form");
+        const float rrev = (MODE == kModeLocked) ? pm.rho_rev - kInv2Pi : pm.rho_rev;
         if constexpr (Q1) {
             PV_FOR_BINS(E, lane, { phc[i] = __builtin_fmaf(pm.rho_rev, ph[i], 0.0f); })
         } else if constexpr (RACC) {
@@ -314,7 +320,7 @@ __device__ __forceinline__ void synth_frame(const float2 (&sv)[Geo<L>::E + 1], b
                 M[i] = __float_as_int(R);
                 phprev[i] = ph[i];
                 const float tj = __builtin_amdgcn_fractf(tqf * __uint_as_float(jkv[i]));
-                phc[i] = __builtin_fmaf(pm.rho_rev, ph[i], R + tj);
+                phc[i] = __builtin_fmaf(rrev, ph[i], R + tj);
             })
         } else {
         PV_FOR_BINS(E, lane, {
@@ -330,19 +336,19 @@ __device__ __forceinline__ void synth_frame(const float2 (&sv)[Geo<L>::E + 1], b
         if (QPOW2) {
             PV_FOR_BINS(E, lane, {
                 const unsigned x = __umul24(pmod, (unsigned)M[i] & (qq - 1u)) + __umul24(tq, jkv[i]);
-                phc[i] = __builtin_fmaf(pm.rho_rev, ph[i], (float)(x & (qq - 1u)) * pm.inv_q);
+                phc[i] = __builtin_fmaf(rrev, ph[i], (float)(x & (qq - 1u)) * pm.inv_q);
             })
         } else if (pm.q_pow2) {
             PV_FOR_BINS(E, lane, {
                 const unsigned x = pmod * ((unsigned)M[i] & (qq - 1u)) + tq * jkv[i];
-                phc[i] = __builtin_fmaf(pm.rho_rev, ph[i], (float)(x & (qq - 1u)) * pm.inv_q);
+                phc[i] = __builtin_fmaf(rrev, ph[i], (float)(x & (qq - 1u)) * pm.inv_q);
             })
         } else {
             PV_FOR_BINS(E, lane, {
                 int mdq = M[i] % (int)qq;
                 mdq += (mdq < 0) ? (int)qq : 0;
                 const unsigned x = pmod * (unsigned)mdq + tq * jkv[i];
-                phc[i] = __builtin_fmaf(pm.rho_rev, ph[i], (float)(x % qq) * pm.inv_q);
+                phc[i] = __builtin_fmaf(rrev, ph[i], (float)(x % qq) * pm.inv_q);
             })
         }
         }  // !RACC
@@ -492,6 +498,18 @@ __device__ __forceinline__ void synth_frame(const float2 (&sv)[Geo<L>::E + 1], b
                 if (k == 0 || k == L) y.y = 0.0f;  // C2R ignores Im of DC and Nyquist
                 Yr[i] = y;
             })
+        } else if constexpr (MODE == kModeLocked) {
+            // every bin takes the phase offset of the peak that owns it and keeps its own
+            // analysis phase: phi[k] + theta[own(k)] (a peak: its unlocked phase, up to rounding)
+            float tho[E + 1];
+            lock_offsets<L>(mag, phc, lane, reinterpret_cast<float*>(tile), tho);
+            PV_FOR_BINS(E, lane, {
+                float sn, cs;
+                sincos_rev(__builtin_fmaf(kInv2Pi, ph[i], tho[i]), &sn, &cs);
+                float2 y = make_float2(mag[i] * cs, mag[i] * sn);
+                if (k == 0 || k == L) y.y = 0.0f;
+                Yr[i] = y;
+            })
         } else {
             PV_FOR_BINS(E, lane, {
                 float sn, cs;
@@ -529,7 +547,7 @@ __device__ __forceinline__ void synth_frame(const float2 (&sv)[Geo<L>::E + 1], b
         Bp[q].x = __int_as_float(__builtin_amdgcn_ds_bpermute(src_lane, __float_as_int(o.x)));
         Bp[q].y = __int_as_float(__builtin_amdgcn_ds_bpermute(src_lane, __float_as_int(o.y)));
     }
-    wave_lds_sync();  // the FFT's first tile store stays after the reads above (MODE 2, 3)
+    wave_lds_sync();  // the FFT's first tile store stays after the reads above (MODE 2, 3, locked)
 #pragma unroll
     for (int q = 0; q < E; ++q) {
         const float2 A = Yr[q];

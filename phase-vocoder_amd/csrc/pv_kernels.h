@@ -203,6 +203,10 @@ hipError_t launch_carry(int channels, const ScanParams& p, hipStream_t s);
 hipError_t launch_segsum(const SegParams& p, hipStream_t s);
 hipError_t launch_segcarry(const SegParams& p, hipStream_t s);
 hipError_t launch_synthesis(int L, int mode, int channels, const SynParams& p, hipStream_t s);
+// STANDARD time stretch with identity phase locking (pv_locked.hip): launch_synthesis's mode 0
+// with every bin's output phase taken from the magnitude peak that owns it; same SynParams
+// (k_lane and src_hi are not used), same tails for launch_seam
+hipError_t launch_synthesis_locked(int L, int channels, const SynParams& p, hipStream_t s);
 // the synthesis kernel for this geometry can take SynParams.k_lane (register overlap-add,
 // power-of-two q, STANDARD)
 bool synthesis_lane_kernel(int L, int mode, int hs, bool q_pow2, unsigned long long q);

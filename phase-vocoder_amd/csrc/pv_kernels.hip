@@ -430,21 +430,7 @@ hipError_t launch_window_gain(const float* win, float* dwin, float* gain, int n,
 }
 
 // ------------------------------------------------------------------ launchers
-template <int L>
-static size_t syn_lds(int dt) {
-    const int ring_floats = (dt > 0) ? 0 : 4 * 2 * L;               // ROLA: tails alias the tiles
-    const int gain_floats = (dt > 0 && (L <= 512 || (L == 1024 && dt == 4))) ? 0 : 2 * L;  // syn_gains_in_regs
-    return sizeof(float2) * (L + (L + 2) + 4 * Geo<L>::TILE) +
-           sizeof(float) * (ring_floats + gain_floats) + sizeof(float) * 4 * (L + 1 + 3);
-}
-
-// register overlap-add slots per frame (out hop = 128 DT), 0 = LDS ring
-static int syn_dt(int L, int hs) {
-    if (L > 1024 || hs % 128 != 0) return 0;
-    const int d = hs / 128;
-    return (d == 1 || d == 2 || d == 4) ? d : 0;
-}
-
+// (syn_lds, syn_dt: pv_syn_run.hpp)
 size_t synthesis_lds_bytes(int L, int hs) {
     const int dt = syn_dt(L, hs);
     switch (L) {

@@ -9,6 +9,8 @@
 //     --N 256 --hopdiv 2 --scale 1       PhaseVocoder(256, effect, 1, 2)  (main.cpp:84)
 //     --mode ref|std                     REF_COMPAT (default) or PV_STANDARD
 //     --batched                          all channels in one pv_process call
+//     --phase-lock                       identity phase locking (pv_set_phase_lock): --mode std
+//                                        time stretch only, not with --rt
 //     --single-arg                       PhaseVocoder(N): periodic Hann, hop N/2 (phaseVocoder.h:46-78)
 //     --nan-faithful                     atanf(0/0) = NaN phases as the reference (kernel.cu:101-109)
 //     --timer                            print CudaPhase::timer() per call (main.cpp:238-241, 275-278)
@@ -72,7 +74,7 @@ int main(int argc, char** argv) {
     Effect effect = TIME_SHIFT;
     int N = 256, hopdiv = 2;
     float scale = 1.0f;
-    bool batched = false, single_arg = false, show_timer = false, rt = false;
+    bool batched = false, single_arg = false, show_timer = false, rt = false, phase_lock = false;
     double ana_ms = 0.0, syn_ms = 0.0;
     pv_mode mode = PV_MODE_REF_COMPAT;
     std::vector<std::string> pos;
@@ -88,6 +90,7 @@ int main(int argc, char** argv) {
         else if (a == "--timer") show_timer = true;
         else if (a == "--dump-f32" && i + 1 < argc) dump = argv[++i];
         else if (a == "--rt") rt = true;
+        else if (a == "--phase-lock") phase_lock = true;
         else pos.push_back(a);
     }
     if (pos.size() >= 1) in = pos[0];                                    // main.cpp:69-81
@@ -119,6 +122,16 @@ int main(int argc, char** argv) {
         single_arg ? new PhaseVocoder(N, numChannels > 0 ? numChannels : 1, cap)  // phaseVocoder.h:46
                    : new PhaseVocoder(N, effect, scale, hopdiv, mode, numChannels > 0 ? numChannels : 1, cap));
     PhaseVocoder& phase = *owner;
+    if (phase_lock) {
+        if (rt) {
+            std::fprintf(stderr, "err: --phase-lock: the real-time path has no phase locking\n");
+            return 1;
+        }
+        if (pv_set_phase_lock(phase.handle, 1) != PV_OK) {
+            std::fprintf(stderr, "err: --phase-lock: %s\n", pv_last_error());
+            return 1;
+        }
+    }
     const int outLen = (int)(phase.timeScale * numSamples);
     std::vector<std::vector<float>> outFile(2, std::vector<float>(outLen > 0 ? outLen : 0, 0.f));
 

@@ -128,6 +128,10 @@ def lib():
     L.pv_process.restype = i
     L.pv_reserve_spectrum.argtypes = [vp]
     L.pv_reserve_spectrum.restype = i
+    L.pv_set_phase_lock.argtypes = [vp, i]
+    L.pv_set_phase_lock.restype = i
+    L.pv_get_phase_lock.argtypes = [vp]
+    L.pv_get_phase_lock.restype = i
     L.pv_export_tables.argtypes = [vp, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), vp]
     L.pv_export_tables.restype = i
     L.pv_import_tables.argtypes = [vp, vp, ctypes.c_size_t, vp]

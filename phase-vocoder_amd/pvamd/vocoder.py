@@ -43,13 +43,15 @@ class PhaseVocoder:
                  hop: int = 2, *, mode: str = REF_COMPAT, max_channels: int = 1,
                  max_frames: int = 4096, device: int = 0, exit_on_error: bool = False,
                  window: int = _lib.PV_WINDOW_DEFAULT, nan_faithful: bool = False,
-                 spec_layout: int = _lib.PV_SPEC_NATURAL, tables_external: bool = False):
+                 spec_layout: int = _lib.PV_SPEC_NATURAL, tables_external: bool = False,
+                 phase_lock: bool = False):
         """window: PV_WINDOW_DEFAULT (the mode's), PV_WINDOW_HAMMING_REF or
         PV_WINDOW_HANN_REF (the 1-argument constructor's, phaseVocoder.h:64-66; see
         `single_arg`); nan_faithful: REF_COMPAT atanf(0/0) = NaN (kernel.cu:101-109);
         spec_layout: PV_SPEC_NATURAL or PV_SPEC_PACKED (STANDARD: bin N/2 folded into slot 0,
         see `unpack_spec`); tables_external: build no tables — `import_tables` (or
-        pvamd.dist.broadcast_tables) must load them before any compute call."""
+        pvamd.dist.broadcast_tables) must load them before any compute call; phase_lock:
+        identity phase locking (STANDARD time stretch only, see `set_phase_lock`)."""
         self.exit_on_error = exit_on_error
         eff = effect if isinstance(effect, int) else ord(effect)
         m = PV_MODE_REF_COMPAT if mode == REF_COMPAT else PV_MODE_STANDARD
@@ -60,9 +62,7 @@ class PhaseVocoder:
         self._L = _lib.lib()
         self._call(self._L.pv_create(ctypes.byref(cfg), ctypes.byref(h)), "pv_create")
         self._h = h
-        info = _lib.new_info()
-        self._call(self._L.pv_get_info(self._h, ctypes.byref(info)), "pv_get_info")
-        self.info = info
+        info = self._read_info()
         self.device = int(device)
         self.mode = mode
         self.effect = chr(eff)
@@ -75,11 +75,31 @@ class PhaseVocoder:
         self.spec_bins = info.spec_bins
         self.spec_stride = info.spec_stride
         self.frames_per_run = info.frames_per_run
+        self.lane_constants = info.lane_constants
+        self.spec_layout = info.spec_layout
+        if phase_lock:
+            self.set_phase_lock(True)
+
+    def _read_info(self):
+        info = _lib.new_info()
+        self._call(self._L.pv_get_info(self._h, ctypes.byref(info)), "pv_get_info")
+        self.info = info
         # 0 split path, 1 single q = 1 launch (pv_fused.hip)
         self.single_launch = info.single_launch
         self.single_launch_frames = info.single_launch_frames
-        self.lane_constants = info.lane_constants
-        self.spec_layout = info.spec_layout
+        return info
+
+    def set_phase_lock(self, lock: bool = True):
+        """pv_set_phase_lock: identity phase locking of the STANDARD time stretch — every bin
+        takes the phase advance of the nearest magnitude peak of its frame, which keeps the
+        bins of one partial coherent (no "phasiness").  Applies to the calls made after it;
+        a single-launch handle runs the split path while locking is on."""
+        self._call(self._L.pv_set_phase_lock(self._h, 1 if lock else 0), "pv_set_phase_lock")
+        self._read_info()
+
+    @property
+    def phase_lock(self) -> bool:
+        return bool(self._L.pv_get_phase_lock(self._h))
 
     @classmethod
     def single_arg(cls, samples: int, **kw):
