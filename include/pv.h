@@ -73,7 +73,9 @@ extern "C" {
                              5: pv_config.tables_external, pv_process(spec = NULL) on the
                                 single launch (later additions are functions only, no
                                 struct change: pv_sources_sha, pv_reserve_spectrum,
-                                pv_segment_*, pv_set_phase_lock / pv_get_phase_lock) */
+                                pv_segment_*, pv_set_phase_lock / pv_get_phase_lock,
+                                pv_set_formant / pv_get_formant, pv_spectral_envelope,
+                                pv_harmonizer_set_formant) */
 
 typedef struct pv_handle pv_handle;
 
@@ -252,8 +254,8 @@ pv_status pv_segment_resynthesis(pv_handle* h, const pv_float2* spec, long long 
  * output is the same bits as with a spectrum buffer. */
 /* allocate (once, zeroed) the handle's own spectrum rows that pv_process(spec = NULL) uses
  * on the split path, so that such calls can then be captured into a graph; thread-safe; a
- * no-op for a single-launch handle (unless phase locking is on).  Not capturable itself (it
- * allocates). */
+ * no-op for a single-launch handle (unless phase locking or formant preservation is on).  Not
+ * capturable itself (it allocates). */
 pv_status pv_reserve_spectrum(pv_handle* h);
 
 pv_status pv_process(pv_handle* h, const float* x, long long ldx, long long n_samples,
@@ -276,6 +278,39 @@ pv_status pv_process(pv_handle* h, const float* x, long long ldx, long long n_sa
  * for the calls enqueued after it.  pv_rt and the harmoniser have no such switch. */
 pv_status pv_set_phase_lock(pv_handle* h, int lock);
 int pv_get_phase_lock(const pv_handle* h);
+
+/* Formant-preserving STANDARD pitch shift (cepstral spectral envelope).  The
+ * plain pitch shift moves the spectral envelope with the partials (a voice shifted by 1.5 has
+ * its formants 1.5 times too high).  With order > 0, per frame: lg[k] = ln max(mag[k], 2^-30)
+ * (maxNum: a NaN magnitude gives the floor), k = 0 .. N/2, extended evenly to N points;
+ * c = irfft(lg), c[n] = 0 wherever min(n, N - n) > order; le = Re rfft(c) is the log envelope;
+ * output bin k' gets the magnitude exp(le[k']) * sum over its source bins k of
+ * mag[k] * exp(-le[k]) (source order, zero without a source) and the plain pitch shift's phase:
+ * the source is whitened, the excitation shifted, and the input's own envelope put back at the
+ * target bin.  At ratio 1 the output is the plain one up to rounding.  The analysis, the spectrum
+ * rows, the unwrap decisions and the stream segments are unchanged: the feature keeps no state
+ * between frames.
+ * order = 0 (default): off.  order in [1, N/4]: on.  Other values: PV_ERR_ARG.  STANDARD +
+ * PV_PITCH_SHIFT handles; otherwise PV_ERR_UNSUPPORTED.  A setup call (not capturable), ordered
+ * like the handle's compute calls.  The first call with order > 0 allocates, zeroed, the handle's
+ * envelope rows: max_channels x max_frames rows of N/2 + 16 floats (bin N/2 and 15 zeros, so
+ * that every row store is whole 64-byte segments), 4 (N/2 + 16) bytes per frame — about 3.6 GB
+ * for 1024 channels x 861 frames at N = 2048; PV_ERR_NOMEM if that fails, and the feature stays
+ * off.  While it is on, pv_resynthesis, pv_process and pv_segment_resynthesis run the envelope
+ * kernel and then the formant synthesis kernel; a single-launch handle takes the split path
+ * (pv_info.single_launch reads 0, pv_process(spec = NULL) uses the handle's own rows:
+ * pv_reserve_spectrum) and goes back to the single launch with order 0; pv_process(spec = NULL)
+ * analyses every bin (the envelope at the target bins reads magnitudes above N/2 / scale).
+ * pv_rt has no such switch. */
+pv_status pv_set_formant(pv_handle* h, int order);
+int pv_get_formant(const pv_handle* h);
+
+/* The log envelope rows of analysed frames, by the same kernel:
+ * env[c*ld_env + t*(N/2 + 8) + k] = le[k], k = 0 .. N/2 (rows of N/2 + 8 floats — the natural
+ * layout's spec_stride; a packed handle's N/2 slots cannot hold the N/2 + 1 values), order in
+ * [1, N/4].  Any STANDARD handle, natural or packed spectrum rows; no state, capturable. */
+pv_status pv_spectral_envelope(pv_handle* h, const pv_float2* spec, long long ld_spec, int channels,
+                               int frames, int order, float* env, long long ld_env, void* stream);
 
 /* ---------------------------------------------------------------- real-time mode
  * A pv_rt streams `channels` mono channels through the STANDARD pipeline one callback at a
@@ -318,6 +353,9 @@ pv_status pv_harmonize(pv_harmonizer* hz, const float* x, long long ldx, long lo
                        int channels, int frames, pv_float2* spec, long long ld_spec, float* voices_out,
                        long long ldo, long long ld_voice, const float* gains, float* mix,
                        long long ld_mix, void* stream);
+/* pv_set_formant for every voice (same arguments and refusals): the envelope is computed once
+ * per pv_harmonize call from the shared analysis into voice 0's rows, which every voice reads */
+pv_status pv_harmonizer_set_formant(pv_harmonizer* hz, int order);
 
 /* ---------------------------------------------------------------- standalone FFT
  * Batched unnormalised complex FFT (both directions, like the reference's GPU_FFT):

@@ -38,10 +38,11 @@ pv_status fail(pv_status s, const std::string& msg) {
     } while (0)
 
 constexpr double kPi = 3.14159265358979323846;
-constexpr int kNumKernels = 9;
+constexpr int kNumKernels = 11;
 const char* kKernelNames[kNumKernels] = {"analysis", "runsum", "carry", "synthesis",
-                                         "seam", "compat_analysis", "rt", "fused", "synthesis_locked"};
-enum { KA = 0, KRS = 1, KC = 2, KS = 3, KSEAM = 4, KCA = 5, KRT = 6, KF = 7, KSL = 8 };
+                                         "seam", "compat_analysis", "rt", "fused", "synthesis_locked",
+                                         "envelope", "synthesis_formant"};
+enum { KA = 0, KRS = 1, KC = 2, KS = 3, KSEAM = 4, KCA = 5, KRT = 6, KF = 7, KSL = 8, KENV = 9, KSF = 10 };
 
 bool is_pow2(long long v) { return v > 0 && (v & (v - 1)) == 0; }
 
@@ -149,6 +150,12 @@ struct pv_handle {
     int mode = 0, effect = 0, pitch = 0, aligned_hop = 1, nan_faithful = 0;
     int packed = 0;  // PV_SPEC_PACKED rows (STANDARD)
     int phase_lock = 0;  // pv_set_phase_lock: identity phase locking (k_synthesis_locked)
+    // pv_set_formant: lifter order of the formant-preserving pitch shift (0: off), and the
+    // handle's envelope rows [max_channels][max_frames][env_stride] fp32 (allocated once, zeroed;
+    // a harmoniser's voices read voice 0's)
+    int formant = 0;
+    int env_stride = 0;
+    float* d_env = nullptr;
     float scale = 1.0f, rho = 1.0f, inv_q = 1.0f;
     unsigned long long p_mod = 0, q = 1;
     int q_pow2 = 1;
@@ -344,10 +351,35 @@ struct SegState {
 
 // carry_from: unwrap carries already scanned by another handle of the same analysis
 // geometry (the harmoniser's voices share one scan); nullptr = scan here.
+// log envelope rows of `frames` frames per channel (k_envelope)
+pv_status do_envelope(pv_handle* h, const pv_float2* spec, long long ld_spec, int C, int frames, int order,
+                      float* env, long long ld_env, int env_stride, int env_tail, hipStream_t s) {
+    pv::EnvParams e{};
+    e.spec = reinterpret_cast<const float2*>(spec);
+    e.ld_spec = ld_spec;
+    e.spec_stride = h->spec_stride;
+    e.frames = frames;
+    e.F = h->F;
+    e.nruns = nruns_of(h, frames);
+    e.packed = h->packed;
+    e.order = order;
+    e.tw = h->d_tw_syn + (h->L_syn == 1024 ? h->L_syn : 0);  // the v3 pass table (fft_table)
+    e.tws = h->d_tws_syn;
+    e.env = env;
+    e.ld_env = ld_env;
+    e.env_stride = env_stride;
+    e.env_tail = env_tail;
+    PV_LAUNCH(h, KENV, s, pv::launch_envelope(h->L_syn, C, e, s));
+    return PV_OK;
+}
+
+// env_from: envelope rows already computed by another handle of the same analysis (the
+// harmoniser's voices share voice 0's, as they share its carries); nullptr = computed here.
 pv_status do_resynthesis(pv_handle* h, const pv_float2* spec, long long ld_spec, int C, int frames,
                          const float* ola_in, long long ld_ola, float* out, long long ldo,
                          bool have_runsum, hipStream_t s, const int* carry_from = nullptr,
-                         bool force_scan = false, const SegState* seg = nullptr) {
+                         bool force_scan = false, const SegState* seg = nullptr,
+                         const float* env_from = nullptr) {
     if (C == 0 || frames == 0) {
         return PV_OK;
     }
@@ -415,7 +447,20 @@ pv_status do_resynthesis(pv_handle* h, const pv_float2* spec, long long ld_spec,
     p.src_hi = h->src_hi;
     p.t_off = seg ? seg->t_off : 0u;
     const int smode = (h->mode == PV_MODE_REF_COMPAT) ? 1 : (h->pitch ? 2 : 0);
-    if (h->phase_lock)  // (STANDARD + PV_TIME_SHIFT: pv_set_phase_lock)
+    if (h->formant) {  // (STANDARD + PV_PITCH_SHIFT: pv_set_formant)
+        const float* env = env_from ? env_from : h->d_env;
+        if (!env) return fail(PV_ERR_ARG, "formant preservation is on but the handle has no envelope rows");
+        const long long ld_env = (long long)h->cfg.max_frames * h->env_stride;
+        if (!env_from) {
+            pv_status se = do_envelope(h, spec, ld_spec, C, frames, h->formant, h->d_env, ld_env, h->env_stride,
+                                       16, s);
+            if (se != PV_OK) return se;
+        }
+        p.env = env;
+        p.ld_env = ld_env;
+        p.env_stride = h->env_stride;
+        PV_LAUNCH(h, KSF, s, pv::launch_synthesis_formant(h->L_syn, C, p, s));
+    } else if (h->phase_lock)  // (STANDARD + PV_TIME_SHIFT: pv_set_phase_lock)
         PV_LAUNCH(h, KSL, s, pv::launch_synthesis_locked(h->L_syn, C, p, s));
     else
         PV_LAUNCH(h, KS, s, pv::launch_synthesis(h->L_syn, smode, C, p, s));
@@ -574,8 +619,8 @@ pv_status pv_get_info(const pv_handle* h, pv_info* info) {
     info->mode = h->mode;
     info->effect = h->effect;
     info->scale = h->scale;
-    // (phase locking runs on the split path: pv_set_phase_lock)
-    info->single_launch = (h->F_fused > 0 && !h->phase_lock) ? 1 : 0;
+    // (phase locking and formant preservation run on the split path)
+    info->single_launch = (h->F_fused > 0 && !h->phase_lock && !h->formant) ? 1 : 0;
     info->single_launch_frames = info->single_launch ? h->F_fused : 0;
     info->lane_constants = h->k_lane;
     info->spec_layout = h->packed ? PV_SPEC_PACKED : PV_SPEC_NATURAL;
@@ -602,7 +647,7 @@ void pv_destroy(pv_handle* h) {
     void* ptrs[] = {h->d_win, h->d_gain, h->d_ek, h->d_tw_ana, h->d_tws_ana, h->d_tw_syn,
                     h->d_tws_syn, h->d_jk_mod, h->d_src_first, h->d_src_cnt, h->d_runsum,
                     h->d_carry, h->d_tails, h->d_seam_flags, h->d_spec_own, h->d_seg_carry,
-                    h->d_seg_phi};
+                    h->d_seg_phi, h->d_env};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
 #ifdef PV_FUSED_STAMPS
@@ -1026,8 +1071,8 @@ pv_status pv_reserve_spectrum(pv_handle* h) {
     if (!h) return fail(PV_ERR_ARG, "null handle");
     DeviceGuard g(h->cfg.device);
     // the single launch keeps a spec = NULL spectrum on chip (with phase locking on, the
-    // handle's calls take the split path)
-    if (h->F_fused > 0 && !h->phase_lock) return PV_OK;
+    // handle's calls take the split path; with formant preservation on too)
+    if (h->F_fused > 0 && !h->phase_lock && !h->formant) return PV_OK;
     return reserve_spec_own(h);
 }
 
@@ -1042,6 +1087,56 @@ pv_status pv_set_phase_lock(pv_handle* h, int lock) {
 
 int pv_get_phase_lock(const pv_handle* h) { return h ? h->phase_lock : 0; }
 
+// own_rows: allocate the handle's envelope rows (a harmoniser's voices k > 0 read voice 0's)
+static pv_status set_formant(pv_handle* h, int order, bool own_rows) {
+    if (!h) return fail(PV_ERR_ARG, "null handle");
+    if (h->mode != PV_MODE_STANDARD || h->effect != PV_PITCH_SHIFT)
+        return fail(PV_ERR_UNSUPPORTED, "pv_set_formant: STANDARD pitch-shift handles only");
+    if (order < 0 || order > h->N / 4) return fail(PV_ERR_ARG, "pv_set_formant: order must be in [0, N/4]");
+    if (order > 0 && own_rows && !h->d_env) {
+        DeviceGuard g(h->cfg.device);
+        // rows of N/2 + 16 floats: bin N/2 and 15 zeros make every row store whole 64-byte segments
+        const int stride = h->L_syn + 16;
+        const size_t bytes = sizeof(float) * (size_t)std::max(h->cfg.max_channels, 1) *
+                             (size_t)std::max(h->cfg.max_frames, 1) * (size_t)stride;
+        float* p = nullptr;
+        if (hipMalloc(&p, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(PV_ERR_NOMEM, "pv_set_formant: envelope rows");
+        }
+        if (hipMemset(p, 0, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+            (void)hipFree(p);
+            return fail(PV_ERR_HIP, "pv_set_formant: zeroing the envelope rows");
+        }
+        h->d_env = p;
+    }
+    h->env_stride = h->L_syn + 16;
+    h->formant = order;
+    return PV_OK;
+}
+
+pv_status pv_set_formant(pv_handle* h, int order) { return set_formant(h, order, true); }
+
+int pv_get_formant(const pv_handle* h) { return h ? h->formant : 0; }
+
+pv_status pv_spectral_envelope(pv_handle* h, const pv_float2* spec, long long ld_spec, int channels, int frames,
+                               int order, float* env, long long ld_env, void* stream) {
+    pv_status st = check_common(h, channels, frames);
+    if (st != PV_OK) return st;
+    if (h->mode != PV_MODE_STANDARD) return fail(PV_ERR_UNSUPPORTED, "pv_spectral_envelope: STANDARD handles only");
+    if (order < 1 || order > h->N / 4) return fail(PV_ERR_ARG, "pv_spectral_envelope: order must be in [1, N/4]");
+    if (channels == 0 || frames == 0) return PV_OK;
+    if (!spec || !env) return fail(PV_ERR_ARG, "null spec/env");
+    if (ld_spec < (long long)frames * h->spec_stride) return fail(PV_ERR_ARG, "ld_spec < frames * spec_stride");
+    // rows of N/2 + 8 floats, the natural layout's spec_stride (a packed handle's N/2 slots
+    // cannot hold the N/2 + 1 values)
+    const int stride = h->L_syn + 8;
+    if (ld_env < (long long)frames * stride) return fail(PV_ERR_ARG, "ld_env < frames * (N/2 + 8)");
+    DeviceGuard g(h->cfg.device);
+    ProfCall pc_(h);
+    return do_envelope(h, spec, ld_spec, channels, frames, order, env, ld_env, stride, 1, (hipStream_t)stream);
+}
+
 pv_status pv_process(pv_handle* h, const float* x, long long ldx, long long n_samples,
                      int channels, int frames, pv_float2* spec, long long ld_spec, float* out,
                      long long ldo, void* stream) {
@@ -1050,7 +1145,7 @@ pv_status pv_process(pv_handle* h, const float* x, long long ldx, long long n_sa
     DeviceGuard g(h->cfg.device);
     ProfCall pc_(h);
     hipStream_t s = (hipStream_t)stream;
-    if (h->F_fused > 0 && !h->phase_lock)
+    if (h->F_fused > 0 && !h->phase_lock && !h->formant)
         return do_fused(h, x, ldx, n_samples, channels, frames, spec, ld_spec, out, ldo, s);
     // spec == NULL: the rows go through the handle's own buffer, and bins no output bin reads
     // (pitch > 1) are not analysed
@@ -1070,7 +1165,8 @@ pv_status pv_process(pv_handle* h, const float* x, long long ldx, long long n_sa
         }
         spec = h->d_spec_own;
         ld_spec = (long long)h->cfg.max_frames * h->spec_stride;
-        if (h->mode == PV_MODE_STANDARD) src_hi = h->src_hi;
+        // (formant preservation: the envelope at the target bins reads every magnitude)
+        if (h->mode == PV_MODE_STANDARD && !h->formant) src_hi = h->src_hi;
     }
     const bool std_mode = (h->mode == PV_MODE_STANDARD) && h->q > 1;  // run records feed the scan
     st = do_analysis(h, x, ldx, n_samples, channels, frames, spec, ld_spec, std_mode, s, src_hi);
@@ -1578,6 +1674,15 @@ pv_status pv_harmonizer_create(const pv_config* cfg, const float* ratios, int vo
     return PV_OK;
 }
 
+pv_status pv_harmonizer_set_formant(pv_harmonizer* hz, int order) {
+    if (!hz || hz->voices.empty()) return fail(PV_ERR_ARG, "null harmoniser");
+    // voice 0 owns the envelope rows; a refusal leaves every voice as it was
+    pv_status st = set_formant(hz->voices[0], order, true);
+    if (st != PV_OK) return st;
+    for (size_t k = 1; k < hz->voices.size(); ++k) (void)set_formant(hz->voices[k], order, false);
+    return PV_OK;
+}
+
 pv_status pv_harmonize(pv_harmonizer* hz, const float* x, long long ldx, long long n_samples,
                        int channels, int frames, pv_float2* spec, long long ld_spec, float* voices_out,
                        long long ldo, long long ld_voice, const float* gains, float* mix,
@@ -1601,8 +1706,10 @@ pv_status pv_harmonize(pv_harmonizer* hz, const float* x, long long ldx, long lo
                         nullptr, /*force_scan: other voices read h0's carries*/ true);
     if (st != PV_OK) return st;
     for (int k = 1; k < K; ++k) {
+        // (formant preservation: voice 0 computed the envelope rows of the shared analysis)
         st = do_resynthesis(hz->voices[k], spec, ld_spec, channels, frames, nullptr, 0,
-                            voices_out + (long long)k * ld_voice, ldo, true, s, h0->d_carry);
+                            voices_out + (long long)k * ld_voice, ldo, true, s, h0->d_carry, false, nullptr,
+                            hz->voices[k]->formant ? h0->d_env : nullptr);
         if (st != PV_OK) return st;
     }
     if (mix && channels > 0 && frames > 0) {

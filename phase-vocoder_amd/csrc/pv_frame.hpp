@@ -5,6 +5,7 @@
 #pragma once
 #include "pv_device.hpp"
 #include "pv_lock.hpp"
+#include "pv_formant.hpp"
 
 
 namespace pv {
@@ -228,7 +229,8 @@ struct SynLds {
 // phprev updated; add_decision = false for a run's first frame, whose decision the carry
 // already holds), MODE 1 REF_COMPAT (kernel.cu:121-129 y-bug), MODE 5: sv is the output
 // spectrum Y itself (k_fused MODE 4), MODE 6 (kModeLocked): MODE 0 with identity phase
-// locking (pv_lock.hpp).  tq = (t + 1) mod q.
+// locking (pv_lock.hpp), MODE 7 (kModeFormant): MODE 2 with the formant gather of
+// pv_formant.hpp (env: the frame's log envelope row).  tq = (t + 1) mod q.
 // Result: STORE_LAST: time samples in tile (natural order, padded); else the inverse
 // FFT's last-pass registers z (point lane + 64 last_slot(idx)).
 // QPOW2: the output-phase denominator q is a power of two <= 2^24 (compile-time path);
@@ -260,7 +262,8 @@ struct TwReg {
 // unwrap state is neither read nor updated; phc = fma(rho / 2 pi, phi, +0) is bit for bit
 // what the RACC path computes with q = 1 (R = tj = +0).
 template <int L, int MODE, bool STORE_LAST, bool QPOW2 = false, bool KREG = false, bool RACC = false,
-          bool Q1 = false, typename Hook = NoHook, typename TwS = NoTwReg, bool V3X = false>
+          bool Q1 = false, typename Hook = NoHook, typename TwS = NoTwReg, bool V3X = false,
+          typename Env = NoEnv>
 __device__ __forceinline__ void synth_frame(const float2 (&sv)[Geo<L>::E + 1], bool add_decision,
                                             unsigned tq, int (&M)[Geo<L>::E + 1],
                                             float (&phprev)[Geo<L>::E + 1], const PhaseMap& pm,
@@ -268,7 +271,8 @@ __device__ __forceinline__ void synth_frame(const float2 (&sv)[Geo<L>::E + 1], b
                                             float2* tile, int lane, float2 (&z)[Geo<L>::E],
                                             const float (&ekr)[Geo<L>::E + 1],
                                             const unsigned (&jkr)[Geo<L>::E + 1],
-                                            const Hook& hook = Hook{}, const TwS& twr = TwS{}) {
+                                            const Hook& hook = Hook{}, const TwS& twr = TwS{},
+                                            const Env& env = Env{}) {
     using G_ = Geo<L>;
     constexpr int E = G_::E;
     constexpr int B = L + 1;
@@ -356,10 +360,13 @@ __device__ __forceinline__ void synth_frame(const float2 (&sv)[Geo<L>::E + 1], b
 #ifdef PV_ABL_NOGATHER
         if constexpr (false) {
 #else
-        if constexpr (MODE == 2 || MODE == 3) {
+        if constexpr (MODE == 2 || MODE == 3 || MODE == kModeFormant) {
 #endif
             float2 Y[E + 1];
-            if constexpr (MODE == 3) {
+            if constexpr (MODE == kModeFormant) {
+                static_assert(Env::ON || MODE != kModeFormant, "the formant gather needs the envelope row");
+                formant_gather<L>(mag, phc, env.v, pm.multi, srcl, tile, lane, Y);
+            } else if constexpr (MODE == 3) {
                 // at most one source per bin (pitch ratio >= 1): srcl holds each bin's source as a
                 // byte offset into the tile, slot L + 1 (a zero written here every frame) when no
                 // source maps there.  Every lane gathers every bin, bin L included (lanes != 0

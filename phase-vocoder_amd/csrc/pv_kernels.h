@@ -104,6 +104,28 @@ struct SynParams {
                                        // source pitch: the row slots above it are not read)
     unsigned t_off;                    // (index of the first frame in the whole stream) mod q:
                                        // 0 unless a segment of a longer stream
+    // formant-preserving pitch shift (k_synthesis_formant; nullptr otherwise): the frames' log
+    // envelope rows, env[c * ld_env + t * env_stride + k], k <= L (k_envelope)
+    const float* env;
+    long long ld_env;
+    int env_stride;
+};
+
+// log spectral envelope of every frame (k_envelope, pv_formant.hip): the cepstrum of the
+// frame's log magnitude, liftered to |quefrency| <= order, back in the log-spectrum domain
+struct EnvParams {
+    const float2* spec;
+    long long ld_spec;
+    int spec_stride, frames, F, nruns;
+    int packed;                        // PV_SPEC_PACKED rows
+    int order;                         // 1 .. N/4
+    const float2* tw;                  // the v3 pass table of the L-point FFT (both directions)
+    const float2* tws;                 // e^{-2 pi i k/N}, k <= L
+    float* env;                        // env[c * ld_env + t * env_stride + k] = le[k], k <= L
+    long long ld_env;
+    int env_stride;
+    int env_tail;                      // row slots written from L on: 1 (bin L), or 16 (bin L
+                                       // and 15 zeros: the row store is whole 64-byte segments)
 };
 
 // single-launch STANDARD path for q = 1 (pv_fused.hip)
@@ -207,6 +229,11 @@ hipError_t launch_synthesis(int L, int mode, int channels, const SynParams& p, h
 // with every bin's output phase taken from the magnitude peak that owns it; same SynParams
 // (k_lane and src_hi are not used), same tails for launch_seam
 hipError_t launch_synthesis_locked(int L, int channels, const SynParams& p, hipStream_t s);
+// formant-preserving STANDARD pitch shift (pv_formant.hip): the envelope rows, then
+// launch_synthesis's mode 2 with the formant gather (SynParams.env; k_lane and src_hi are not
+// used), same tails for launch_seam.  L <= 1024.
+hipError_t launch_envelope(int L, int channels, const EnvParams& p, hipStream_t s);
+hipError_t launch_synthesis_formant(int L, int channels, const SynParams& p, hipStream_t s);
 // the synthesis kernel for this geometry can take SynParams.k_lane (register overlap-add,
 // power-of-two q, STANDARD)
 bool synthesis_lane_kernel(int L, int mode, int hs, bool q_pow2, unsigned long long q);

@@ -313,13 +313,15 @@ __device__ __forceinline__ void syn_run(const SynParams& p, const SynCarve& sc, 
         for (int q = 0; q < E; ++q) twr.v[q] = lds_ld(&sc.twsl[lane + 64 * q]);
     }
     const unsigned q32 = (unsigned)p.q;  // <= 2^24 (QPOW2) or <= 32768
-    auto synth = [&](int u, int t, const float2 (&sv)[E + 1], float2 (&z)[E], const auto& hk) {
+    // (env: the frame's log envelope row, formant mode; NoEnv otherwise)
+    auto synth = [&](int u, int t, const float2 (&sv)[E + 1], float2 (&z)[E], const auto& hk, const auto& env) {
         // (t_off: a segment's first frame index in its whole stream, mod q)
         const unsigned tq = QPOW2 ? ((unsigned)(t + 1) + p.t_off) & (q32 - 1u) : ((unsigned)(t + 1) + p.t_off) % q32;
         using H = std::decay_t<decltype(hk)>;
+        using EV = std::decay_t<decltype(env)>;
         // (L = 1024: the radix-16/16/4 inverse FFT on the v3 pass table, p.tw)
-        synth_frame<L, MODE, !ROLA, QPOW2, KREG, RACC, false, H, TwS, (L == 1024)>(
-            sv, u > 0, tq, M, phprev, pmap, stb, tw0, tile, lane, z, ekr, jkr, hk, twr);
+        synth_frame<L, MODE, !ROLA, QPOW2, KREG, RACC, false, H, TwS, (L == 1024), EV>(
+            sv, u > 0, tq, M, phprev, pmap, stb, tw0, tile, lane, z, ekr, jkr, hk, twr, env);
     };
     // PV_SPEC_PACKED rows: lane 0 finds bins 0 and L in slot 0 (the row has no slot L)
     const bool packed = p.packed != 0;
@@ -358,11 +360,24 @@ __device__ __forceinline__ void syn_run(const SynParams& p, const SynCarve& sc, 
         for (int s = 0; s < NS; ++s) acc[s] = (s + D < NS) ? acc[(s + D < NS) ? s + D : 0] : make_float2(0.0f, 0.0f);
     };
 
+    // formant mode: the frame's log envelope row (k_envelope wrote it), loaded one frame
+    // ahead like the spectrum row; every lane reads bin L's value (one address)
+    constexpr bool FORMANT = MODE == kModeFormant;
+    using EnvS = typename std::conditional<FORMANT, EnvReg<E>, NoEnv>::type;
+    EnvS ev;
+    auto load_env = [&](int t) {
+        if constexpr (FORMANT) {
+            const float* erow = p.env + (long long)c * p.ld_env + (long long)t * p.env_stride;
+#pragma unroll
+            for (int i = 0; i <= E; ++i) ev.v[i] = erow[(i == E) ? L : lane + 64 * i];
+        }
+    };
     // the self-tracked prefetch needs registers that are never spilled or copied while the
     // loads are in flight: only at L = 512, where the kernels fit without spills and no
     // register copy sits between a row load and its vmcnt (scripts/prefetch_hazards.py,
     // tests/test_abi.py; at L <= 256 the compiler copies the row buffers)
-    constexpr bool FASTOK = ROLA && L == 512;
+    // (the formant synthesis reads its envelope rows with plain loads: no self-tracked prefetch)
+    constexpr bool FASTOK = ROLA && L == 512 && MODE != kModeFormant;
     const bool fast = FASTOK && nfr == p.F && p.out_aligned && obase + (long long)p.F * hs <= p.out_len;
     if (FASTOK && fast) {
         // every store of the run is in bounds: trip u = [load row u+1] [frame u] [D stores]
@@ -380,7 +395,7 @@ __device__ __forceinline__ void syn_run(const SynParams& p, const SynCarve& sc, 
             for (int i = 0; i <= E; ++i) sv[i] = make_float2(row[i].x, row[i].y);
             unpack(sv);
             float2 z[E];
-            synth(u, t0 + u, sv, z, NoHook{});
+            synth(u, t0 + u, sv, z, NoHook{}, ev);
             ola_regs(z);
             flush_regs(u, std::true_type{});  // exactly D stores
         };
@@ -401,7 +416,7 @@ __device__ __forceinline__ void syn_run(const SynParams& p, const SynCarve& sc, 
         // current row (synth_frame's hook, before the pre-step), into the same registers —
         // no copy of the row (34 VGPR moves per frame); the loads have the inverse FFT and
         // the overlap-add to land
-        constexpr bool LATE = ROLA && L >= 1024 && MODE != 2;  // (MODE 2: 260 VGPRs, 1 wave/SIMD)
+        constexpr bool LATE = ROLA && L >= 1024 && MODE != 2 && MODE != kModeFormant;  // (MODE 2: 260 VGPRs, 1 wave/SIMD)
         const bool fast_st = ROLA && p.out_aligned && obase + (long long)p.F * hs <= p.out_len;
         (void)fast_st;
         static_assert(NR == E || (MODE == 3 && NR < E), "partial rows: single-source pitch only");
@@ -415,6 +430,7 @@ __device__ __forceinline__ void syn_run(const SynParams& p, const SynCarve& sc, 
             })
         };
         if (nfr > 0) load_row(specc + (long long)t0 * p.spec_stride);
+        if (nfr > 0) load_env(t0);
         for (int u = 0; u < p.F; ++u) {
             const int t = t0 + u;
             if (u < nfr) {
@@ -424,14 +440,16 @@ __device__ __forceinline__ void syn_run(const SynParams& p, const SynCarve& sc, 
                     // (unconditional: the run's last frame re-reads its own row, so the
                     // registers take no merge of loaded and kept values)
                     const int tn = (u + 1 < nfr) ? t + 1 : t;
-                    synth(u, t, sv, z, [&]() { load_row(specc + (long long)tn * p.spec_stride); });
+                    synth(u, t, sv, z, [&]() { load_row(specc + (long long)tn * p.spec_stride); }, ev);
                 } else {
                 float2 cur[E + 1];
 #pragma unroll
                 for (int i = 0; i <= E; ++i) cur[i] = sv[i];
                 unpack(cur);  // at use: unpacking at the load would wait for it at once
+                const EnvS cev = ev;
                 if (u + 1 < nfr) load_row(specc + (long long)(t + 1) * p.spec_stride);
-                synth(u, t, cur, z, NoHook{});
+                if (u + 1 < nfr) load_env(t + 1);
+                synth(u, t, cur, z, NoHook{}, cev);
                 }
                 if constexpr (ROLA) {
                     ola_regs(z);

@@ -11,6 +11,8 @@
 //     --batched                          all channels in one pv_process call
 //     --phase-lock                       identity phase locking (pv_set_phase_lock): --mode std
 //                                        time stretch only, not with --rt
+//     --formant ORDER                    formant-preserving pitch shift (pv_set_formant, lifter
+//                                        order 1 .. N/4): --mode std pitch shift only, not with --rt
 //     --single-arg                       PhaseVocoder(N): periodic Hann, hop N/2 (phaseVocoder.h:46-78)
 //     --nan-faithful                     atanf(0/0) = NaN phases as the reference (kernel.cu:101-109)
 //     --timer                            print CudaPhase::timer() per call (main.cpp:238-241, 275-278)
@@ -75,6 +77,7 @@ int main(int argc, char** argv) {
     int N = 256, hopdiv = 2;
     float scale = 1.0f;
     bool batched = false, single_arg = false, show_timer = false, rt = false, phase_lock = false;
+    int formant = 0;
     double ana_ms = 0.0, syn_ms = 0.0;
     pv_mode mode = PV_MODE_REF_COMPAT;
     std::vector<std::string> pos;
@@ -91,6 +94,7 @@ int main(int argc, char** argv) {
         else if (a == "--dump-f32" && i + 1 < argc) dump = argv[++i];
         else if (a == "--rt") rt = true;
         else if (a == "--phase-lock") phase_lock = true;
+        else if (a == "--formant" && i + 1 < argc) formant = std::atoi(argv[++i]);
         else pos.push_back(a);
     }
     if (pos.size() >= 1) in = pos[0];                                    // main.cpp:69-81
@@ -129,6 +133,16 @@ int main(int argc, char** argv) {
         }
         if (pv_set_phase_lock(phase.handle, 1) != PV_OK) {
             std::fprintf(stderr, "err: --phase-lock: %s\n", pv_last_error());
+            return 1;
+        }
+    }
+    if (formant != 0) {
+        if (rt) {
+            std::fprintf(stderr, "err: --formant: the real-time path has no formant preservation\n");
+            return 1;
+        }
+        if (pv_set_formant(phase.handle, formant) != PV_OK) {
+            std::fprintf(stderr, "err: --formant: %s\n", pv_last_error());
             return 1;
         }
     }

@@ -132,6 +132,12 @@ def lib():
     L.pv_set_phase_lock.restype = i
     L.pv_get_phase_lock.argtypes = [vp]
     L.pv_get_phase_lock.restype = i
+    L.pv_set_formant.argtypes = [vp, i]
+    L.pv_set_formant.restype = i
+    L.pv_get_formant.argtypes = [vp]
+    L.pv_get_formant.restype = i
+    L.pv_spectral_envelope.argtypes = [vp, vp, ll, i, i, i, vp, ll, vp]
+    L.pv_spectral_envelope.restype = i
     L.pv_export_tables.argtypes = [vp, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), vp]
     L.pv_export_tables.restype = i
     L.pv_import_tables.argtypes = [vp, vp, ctypes.c_size_t, vp]
@@ -172,6 +178,8 @@ def lib():
     L.pv_harmonize.argtypes = [vp, vp, ll, ll, i, i, vp, ll, vp, ll, ll, ctypes.POINTER(ctypes.c_float),
                                vp, ll, vp]
     L.pv_harmonize.restype = i
+    L.pv_harmonizer_set_formant.argtypes = [vp, i]
+    L.pv_harmonizer_set_formant.restype = i
     _lib = L
     return L
 

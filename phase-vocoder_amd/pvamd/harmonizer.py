@@ -11,7 +11,9 @@ from .vocoder import _ptr, _torch
 
 class Harmonizer:
     def __init__(self, samples: int, ratios, hop: int = 4, *, max_channels: int = 1,
-                 max_frames: int = 4096, device: int = 0):
+                 max_frames: int = 4096, device: int = 0, formant: int = 0):
+        """formant: lifter order of the formant-preserving pitch shift for every voice
+        (`set_formant`; 0 = off)."""
         self.ratios = [float(r) for r in ratios]
         K = len(self.ratios)
         cfg = _lib.config(samples, hop, _lib.PV_PITCH_SHIFT, 1.0, _lib.PV_MODE_STANDARD, max_channels,
@@ -26,6 +28,13 @@ class Harmonizer:
         self.nSamps = int(samples)
         self.hopSize = int(samples) // int(hop)
         self.spec_stride = ((self.nSamps // 2 + 1) + 7) & ~7
+        if formant:
+            self.set_formant(formant)
+
+    def set_formant(self, order: int):
+        """pv_harmonizer_set_formant: every voice keeps the input's formants (the envelope is
+        computed once per call from the shared analysis); 0 turns it off."""
+        _lib.check(self._L.pv_harmonizer_set_formant(self._h, int(order)), "pv_harmonizer_set_formant")
 
     def close(self):
         if getattr(self, "_h", None):

@@ -44,14 +44,16 @@ class PhaseVocoder:
                  max_frames: int = 4096, device: int = 0, exit_on_error: bool = False,
                  window: int = _lib.PV_WINDOW_DEFAULT, nan_faithful: bool = False,
                  spec_layout: int = _lib.PV_SPEC_NATURAL, tables_external: bool = False,
-                 phase_lock: bool = False):
+                 phase_lock: bool = False, formant: int = 0):
         """window: PV_WINDOW_DEFAULT (the mode's), PV_WINDOW_HAMMING_REF or
         PV_WINDOW_HANN_REF (the 1-argument constructor's, phaseVocoder.h:64-66; see
         `single_arg`); nan_faithful: REF_COMPAT atanf(0/0) = NaN (kernel.cu:101-109);
         spec_layout: PV_SPEC_NATURAL or PV_SPEC_PACKED (STANDARD: bin N/2 folded into slot 0,
         see `unpack_spec`); tables_external: build no tables — `import_tables` (or
         pvamd.dist.broadcast_tables) must load them before any compute call; phase_lock:
-        identity phase locking (STANDARD time stretch only, see `set_phase_lock`)."""
+        identity phase locking (STANDARD time stretch only, see `set_phase_lock`); formant:
+        lifter order of the formant-preserving pitch shift (STANDARD pitch shift only, see
+        `set_formant`; 0 = off)."""
         self.exit_on_error = exit_on_error
         eff = effect if isinstance(effect, int) else ord(effect)
         m = PV_MODE_REF_COMPAT if mode == REF_COMPAT else PV_MODE_STANDARD
@@ -79,6 +81,8 @@ class PhaseVocoder:
         self.spec_layout = info.spec_layout
         if phase_lock:
             self.set_phase_lock(True)
+        if formant:
+            self.set_formant(formant)
 
     def _read_info(self):
         info = _lib.new_info()
@@ -100,6 +104,33 @@ class PhaseVocoder:
     @property
     def phase_lock(self) -> bool:
         return bool(self._L.pv_get_phase_lock(self._h))
+
+    def set_formant(self, order: int):
+        """pv_set_formant: formant-preserving STANDARD pitch shift — the frame's cepstral
+        envelope (quefrencies up to `order`, 1 .. N/4) is divided out of the source bins and put
+        back at the target bins, so the formants stay where the input has them.  0 turns it
+        off.  Applies to the calls made after it; the first call allocates the handle's
+        envelope rows, and a single-launch handle runs the split path while it is on."""
+        self._call(self._L.pv_set_formant(self._h, int(order)), "pv_set_formant")
+        self._read_info()
+
+    @property
+    def formant(self) -> int:
+        return int(self._L.pv_get_formant(self._h))
+
+    def spectral_envelope(self, spec, order: int, frames: int | None = None, stream=None):
+        """pv_spectral_envelope: spec [C, frames, spec_stride, 2] of a STANDARD handle -> the
+        frames' log envelopes le [C, frames, N/2 + 1] float32 (natural log of the magnitude
+        envelope; a view of rows padded to N/2 + 8)."""
+        torch = _torch()
+        C = spec.shape[0]
+        frames = spec.shape[1] if frames is None else frames
+        B = self.nSamps // 2 + 1
+        env = torch.zeros((C, frames, B + 7), dtype=torch.float32, device=spec.device)
+        self._call(self._L.pv_spectral_envelope(self._h, _ptr(spec), spec.stride(0) // 2, C, frames,
+                                                int(order), _ptr(env), env.stride(0), self._stream(stream)),
+                   "pv_spectral_envelope")
+        return env[..., :B]
 
     @classmethod
     def single_arg(cls, samples: int, **kw):
