@@ -75,7 +75,9 @@ extern "C" {
                                 struct change: pv_sources_sha, pv_reserve_spectrum,
                                 pv_segment_*, pv_set_phase_lock / pv_get_phase_lock,
                                 pv_set_formant / pv_get_formant, pv_spectral_envelope,
-                                pv_harmonizer_set_formant) */
+                                pv_harmonizer_set_formant, pv_resampler_* / pv_resample /
+                                pv_resample_length, pv_pitch_reserve / pv_pitch_process /
+                                pv_pitch_output_length) */
 
 typedef struct pv_handle pv_handle;
 
@@ -311,6 +313,58 @@ int pv_get_formant(const pv_handle* h);
  * [1, N/4].  Any STANDARD handle, natural or packed spectrum rows; no state, capturable. */
 pv_status pv_spectral_envelope(pv_handle* h, const pv_float2* spec, long long ld_spec, int channels,
                                int frames, int order, float* env, long long ld_env, void* stream);
+
+/* ---------------------------------------------------------------- resampler
+ * Band-limited resampling by a rational ratio, and the pitch shift built on it.
+ * p/q is reduced by its gcd to P/Q.  Output sample m sits at input position m P / Q: integer
+ * part i_m = floor(m P / Q), phase r_m = (m P) mod Q (exact 64-bit integers); n_out =
+ * ceil(n_in Q / P), every m with m P / Q < n_in.  P/Q > 1 reads faster: the pitch goes up and
+ * the signal gets shorter.
+ *   quality   0 fast: Z = 16, rolloff = 0.85,               Kaiser beta = 8.555504641634386
+ *             1 best: Z = 64, rolloff = 0.9475937167399596, Kaiser beta = 14.769656459379492
+ *   filter    s = rolloff min(1, Q/P), W = ceil(Z / s),
+ *             h(tau) = s sinc(s tau) I0(beta sqrt(1 - u^2)) / I0(beta), u = s tau / Z, for
+ *             |u| < 1 and 0 otherwise; sinc(x) = sin(pi x) / (pi x)
+ *   output    y[m] = sum_{j = -W+1}^{W} x[i_m + j] h(j - r_m / Q); x reads as 0 outside
+ *             [0, n_in), as pv_analysis reads it past n_samples
+ * Ratio 1 (P = Q) is an exact copy with no filter.  Accepted: 1/4 <= P/Q <= 4 with P, Q <= 4096;
+ * anything else is PV_ERR_UNSUPPORTED; quality other than 0, 1 and p or q <= 0 are PV_ERR_ARG.
+ * The Q x 2W coefficients are built on the host in fp64 (I0 by its power series) and rounded
+ * to fp32 once, by pv_resampler_create (it allocates: not capturable); the kernel accumulates in
+ * fp32 in its own tap order, so the result is tolerance bound like the synthesis (no bit-exact
+ * contract; pv_contract_version is not concerned). */
+typedef struct pv_resampler pv_resampler;
+pv_status pv_resampler_create(int p, int q, int quality, int device, pv_resampler** out);
+void pv_resampler_destroy(pv_resampler* rs);
+/* n_out for n_in input samples (0 for a NULL resampler or n_in <= 0) */
+long long pv_resample_length(const pv_resampler* rs, long long n_in);
+/* y[c*ldy + m], m < pv_resample_length(rs, n_in), from x[c*ldx + i], i < n_in, c < channels:
+ * device pointers on the resampler's device; x and y must not overlap (PV_ERR_ARG).  channels
+ * or n_in 0: nothing is done (PV_OK).  One launch, no allocation, no synchronisation: capturable. */
+pv_status pv_resample(pv_resampler* rs, const float* x, long long ldx, long long n_in, int channels,
+                      float* y, long long ldy, void* stream);
+
+/* Pitch shift by time stretch and resampling, on a STANDARD + PV_TIME_SHIFT handle: the handle's
+ * stretch by out_hop / hop, then a resampling by P/Q = out_hop / hop, restores the duration and
+ * moves the pitch by the realised ratio out_hop / hop.  Unlike the bin-mapping PV_PITCH_SHIFT it
+ * keeps the bins of a partial together, and it honours pv_set_phase_lock.
+ * pv_pitch_reserve (a setup call, not capturable) builds the handle's resampler of the given
+ * quality and allocates its scratch rows, max_channels x pv_output_length(h, max_frames) floats
+ * (PV_ERR_NOMEM: the feature stays off); calling it again replaces the quality.
+ * pv_pitch_process is exactly pv_process into the scratch rows, then pv_resample into out (same
+ * arguments and spec semantics as pv_process, spec = NULL included; capturable under pv_process's
+ * conditions); out[c*ldo + m], m < pv_pitch_output_length(h, frames) =
+ * pv_resample_length of pv_output_length(h, frames).  At out_hop = hop it is pv_process, bit for
+ * bit.
+ * REF_COMPAT or PV_PITCH_SHIFT handle: PV_ERR_UNSUPPORTED; out_hop / hop outside [1/4, 4]:
+ * PV_ERR_UNSUPPORTED; bad quality: PV_ERR_ARG; pv_pitch_process before a successful
+ * pv_pitch_reserve: PV_ERR_ARG; NULL handle: PV_ERR_ARG (0 from the length call).
+ * pv_rt, the harmoniser and the stream segments have no such form. */
+pv_status pv_pitch_reserve(pv_handle* h, int quality);
+long long pv_pitch_output_length(const pv_handle* h, int frames);
+pv_status pv_pitch_process(pv_handle* h, const float* x, long long ldx, long long n_samples,
+                           int channels, int frames, pv_float2* spec, long long ld_spec, float* out,
+                           long long ldo, void* stream);
 
 /* ---------------------------------------------------------------- real-time mode
  * A pv_rt streams `channels` mono channels through the STANDARD pipeline one callback at a

@@ -19,6 +19,7 @@
 
 #include "../../include/pv.h"
 #include "pv_kernels.h"
+#include "pv_resample.hpp"
 
 namespace {
 
@@ -38,11 +39,11 @@ pv_status fail(pv_status s, const std::string& msg) {
     } while (0)
 
 constexpr double kPi = 3.14159265358979323846;
-constexpr int kNumKernels = 11;
+constexpr int kNumKernels = 12;
 const char* kKernelNames[kNumKernels] = {"analysis", "runsum", "carry", "synthesis",
                                          "seam", "compat_analysis", "rt", "fused", "synthesis_locked",
-                                         "envelope", "synthesis_formant"};
-enum { KA = 0, KRS = 1, KC = 2, KS = 3, KSEAM = 4, KCA = 5, KRT = 6, KF = 7, KSL = 8, KENV = 9, KSF = 10 };
+                                         "envelope", "synthesis_formant", "resample"};
+enum { KA = 0, KRS = 1, KC = 2, KS = 3, KSEAM = 4, KCA = 5, KRT = 6, KF = 7, KSL = 8, KENV = 9, KSF = 10, KRES = 11 };
 
 bool is_pow2(long long v) { return v > 0 && (v & (v - 1)) == 0; }
 
@@ -156,6 +157,11 @@ struct pv_handle {
     int formant = 0;
     int env_stride = 0;
     float* d_env = nullptr;
+    // pv_pitch_reserve: the resampler of pv_pitch_process (P = out hop, Q = hop) and the scratch
+    // rows the time stretch writes for it, [max_channels][ld_pitch] fp32
+    pv_resampler* pitch_rs = nullptr;
+    float* d_pitch = nullptr;
+    long long ld_pitch = 0;
     float scale = 1.0f, rho = 1.0f, inv_q = 1.0f;
     unsigned long long p_mod = 0, q = 1;
     int q_pow2 = 1;
@@ -650,6 +656,8 @@ void pv_destroy(pv_handle* h) {
                     h->d_seg_phi, h->d_env};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
+    if (h->d_pitch) (void)hipFree(h->d_pitch);
+    pv_resampler_destroy(h->pitch_rs);
 #ifdef PV_FUSED_STAMPS
     if (h->d_stamps) (void)hipFree(h->d_stamps);
 #endif
@@ -1137,14 +1145,11 @@ pv_status pv_spectral_envelope(pv_handle* h, const pv_float2* spec, long long ld
     return do_envelope(h, spec, ld_spec, channels, frames, order, env, ld_env, stride, 1, (hipStream_t)stream);
 }
 
-pv_status pv_process(pv_handle* h, const float* x, long long ldx, long long n_samples,
-                     int channels, int frames, pv_float2* spec, long long ld_spec, float* out,
-                     long long ldo, void* stream) {
-    pv_status st = check_common(h, channels, frames);
-    if (st != PV_OK) return st;
-    DeviceGuard g(h->cfg.device);
-    ProfCall pc_(h);
-    hipStream_t s = (hipStream_t)stream;
+// pv_process after its checks (the caller holds the device guard and the profile call)
+static pv_status process_impl(pv_handle* h, const float* x, long long ldx, long long n_samples, int channels,
+                              int frames, pv_float2* spec, long long ld_spec, float* out, long long ldo,
+                              hipStream_t s) {
+    pv_status st = PV_OK;
     if (h->F_fused > 0 && !h->phase_lock && !h->formant)
         return do_fused(h, x, ldx, n_samples, channels, frames, spec, ld_spec, out, ldo, s);
     // spec == NULL: the rows go through the handle's own buffer, and bins no output bin reads
@@ -1174,6 +1179,16 @@ pv_status pv_process(pv_handle* h, const float* x, long long ldx, long long n_sa
     // (single-source pitch: the synthesis reads only the row slots of bins <= src_hi, the
     // ones the analysis wrote, k_synthesis NR)
     return do_resynthesis(h, spec, ld_spec, channels, frames, nullptr, 0, out, ldo, std_mode, s);
+}
+
+pv_status pv_process(pv_handle* h, const float* x, long long ldx, long long n_samples,
+                     int channels, int frames, pv_float2* spec, long long ld_spec, float* out,
+                     long long ldo, void* stream) {
+    pv_status st = check_common(h, channels, frames);
+    if (st != PV_OK) return st;
+    DeviceGuard g(h->cfg.device);
+    ProfCall pc_(h);
+    return process_impl(h, x, ldx, n_samples, channels, frames, spec, ld_spec, out, ldo, (hipStream_t)stream);
 }
 
 }  // extern "C"
@@ -1727,6 +1742,231 @@ pv_status pv_harmonize(pv_harmonizer* hz, const float* x, long long ldx, long lo
         hipError_t e = pv::launch_mix(mp, s);
         if (e != hipSuccess) return fail(PV_ERR_HIP, std::string("mix launch: ") + hipGetErrorString(e));
     }
+    return PV_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- resampler
+// pv_resampler: a reduced ratio P:Q, a quality preset and the polyphase coefficient table in
+// device memory (pv_resample.hpp); pv_pitch_process: a STANDARD time stretch into the handle's
+// scratch rows, resampled by out_hop : hop.
+struct pv_resampler {
+    int P = 1, Q = 1, quality = 0, device = 0;
+    pv::ResamplePlan plan{};
+    float4* d_tab = nullptr;  // nullptr at ratio 1: the rows are copied
+};
+
+namespace {
+
+// {Z, rolloff, Kaiser beta} of the quality presets (include/pv.h)
+const double kResamplePresets[2][3] = {{16.0, 0.85, 8.555504641634386},
+                                       {64.0, 0.9475937167399596, 14.769656459379492}};
+
+// modified Bessel function I0 by its power series sum_k ((x / 2)^k / k!)^2
+double bessel_i0(double x) {
+    const double q = 0.25 * x * x;
+    double term = 1.0, sum = 1.0;
+    for (int k = 1; k < 500; ++k) {
+        term *= q / ((double)k * (double)k);
+        sum += term;
+        if (term < 1e-17 * sum) break;
+    }
+    return sum;
+}
+
+long long gcd_ll(long long a, long long b) {
+    while (b) {
+        const long long t = a % b;
+        a = b;
+        b = t;
+    }
+    return a;
+}
+
+// the eight alignments of the Q x 2W coefficient table (pv_resample.hpp ResampleParams::tab),
+// fp64 rounded to fp32 once
+void resample_table(int P, int Q, int quality, const pv::ResamplePlan& plan, std::vector<float>& tab) {
+    const double Z = kResamplePresets[quality][0], rolloff = kResamplePresets[quality][1],
+                 beta = kResamplePresets[quality][2];
+    const double s = rolloff * std::min(1.0, (double)Q / (double)P);
+    const double i0b = bessel_i0(beta);
+    const int W = plan.W, NC = plan.NC;
+    std::vector<float> row(2 * W);
+    tab.assign((size_t)8 * Q * NC * 4, 0.0f);
+    for (int r = 0; r < Q; ++r) {
+        for (int t = 0; t < 2 * W; ++t) {
+            const double tau = (double)(t - W + 1) - (double)r / (double)Q;
+            const double u = s * tau / Z;
+            double v = 0.0;
+            if (std::fabs(u) < 1.0) {
+                const double a = kPi * s * tau;
+                const double sinc = (a == 0.0) ? 1.0 : std::sin(a) / a;
+                v = s * sinc * bessel_i0(beta * std::sqrt(1.0 - u * u)) / i0b;
+            }
+            row[t] = (float)v;
+        }
+        for (int off = 0; off < 8; ++off) {
+            float* dst = tab.data() + ((size_t)off * Q + r) * NC * 4;
+            for (int t = 0; t < 2 * W; ++t) dst[t + off] = row[t];
+        }
+    }
+}
+
+long long resample_length(int P, int Q, long long n_in) {
+    if (n_in <= 0) return 0;
+    return (n_in * Q + P - 1) / P;
+}
+
+// the launch of pv_resample / pv_pitch_process (arguments checked by the caller)
+hipError_t resample_rows(const pv_resampler* rs, const float* x, long long ldx, long long n_in, int channels,
+                         float* y, long long ldy, hipStream_t s) {
+    if (!rs->d_tab) return pv::launch_copy_rows(x, ldx, y, ldy, n_in, channels, s);
+    pv::ResampleParams p{};
+    p.x = x;
+    p.ldx = ldx;
+    p.n_in = n_in;
+    p.y = y;
+    p.ldy = ldy;
+    p.n_out = resample_length(rs->P, rs->Q, n_in);
+    p.tab = rs->d_tab;
+    p.P = rs->P;
+    p.Q = rs->Q;
+    p.plan = rs->plan;
+    const long long T = (long long)rs->plan.R * rs->plan.D;
+    const long long ntiles = (p.n_out + T - 1) / T;
+    if (ntiles > 0x7fffffffLL) return hipErrorInvalidValue;
+    p.ntiles = (int)ntiles;
+    return pv::launch_resample(channels, p, s);
+}
+
+}  // namespace
+
+extern "C" {
+
+pv_status pv_resampler_create(int p, int q, int quality, int device, pv_resampler** out) {
+    if (!out) return fail(PV_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (p <= 0 || q <= 0) return fail(PV_ERR_ARG, "pv_resampler_create: p and q must be positive");
+    if (quality != 0 && quality != 1) return fail(PV_ERR_ARG, "pv_resampler_create: quality must be 0 (fast) or 1 (best)");
+    const long long g = gcd_ll(p, q);
+    const long long P = p / g, Q = q / g;
+    if (P > 4096 || Q > 4096 || P > 4 * Q || Q > 4 * P)
+        return fail(PV_ERR_UNSUPPORTED, "pv_resampler_create: ratio in [1/4, 4] with reduced p, q <= 4096");
+    pv_resampler* rs = new pv_resampler();
+    rs->P = (int)P;
+    rs->Q = (int)Q;
+    rs->quality = quality;
+    rs->device = device;
+    if (P != Q) {
+        const double s = kResamplePresets[quality][1] * std::min(1.0, (double)Q / (double)P);
+        const int W = (int)std::ceil(kResamplePresets[quality][0] / s);
+        if (!pv::resample_plan(rs->P, rs->Q, W, &rs->plan)) {
+            delete rs;
+            return fail(PV_ERR_UNSUPPORTED, "pv_resampler_create: no tile plan for this ratio");
+        }
+        std::vector<float> tab;
+        resample_table(rs->P, rs->Q, quality, rs->plan, tab);
+        DeviceGuard dg(device);
+        if (hipMalloc((void**)&rs->d_tab, sizeof(float) * tab.size()) != hipSuccess) {
+            (void)hipGetLastError();
+            delete rs;
+            return fail(PV_ERR_NOMEM, "pv_resampler_create: coefficient table");
+        }
+        if (hipMemcpy(rs->d_tab, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(rs->d_tab);
+            delete rs;
+            return fail(PV_ERR_HIP, "pv_resampler_create: uploading the coefficient table");
+        }
+    }
+    *out = rs;
+    return PV_OK;
+}
+
+void pv_resampler_destroy(pv_resampler* rs) {
+    if (!rs) return;
+    if (rs->d_tab) {
+        DeviceGuard dg(rs->device);
+        (void)hipFree(rs->d_tab);
+    }
+    delete rs;
+}
+
+long long pv_resample_length(const pv_resampler* rs, long long n_in) {
+    return rs ? resample_length(rs->P, rs->Q, n_in) : 0;
+}
+
+pv_status pv_resample(pv_resampler* rs, const float* x, long long ldx, long long n_in, int channels, float* y,
+                      long long ldy, void* stream) {
+    if (!rs) return fail(PV_ERR_ARG, "null resampler");
+    if (channels < 0 || n_in < 0) return fail(PV_ERR_ARG, "negative channels / n_in");
+    if (channels == 0 || n_in == 0) return PV_OK;
+    if (!x || !y) return fail(PV_ERR_ARG, "null x/y");
+    const long long n_out = resample_length(rs->P, rs->Q, n_in);
+    if (channels > 1 && (ldx < n_in || ldy < n_out)) return fail(PV_ERR_ARG, "ldx < n_in or ldy < pv_resample_length");
+    const float* xe = x + (channels - 1) * ldx + n_in;
+    const float* ye = y + (channels - 1) * ldy + n_out;
+    if ((uintptr_t)x < (uintptr_t)ye && (uintptr_t)y < (uintptr_t)xe) return fail(PV_ERR_ARG, "x and y overlap");
+    DeviceGuard dg(rs->device);
+    const hipError_t e = resample_rows(rs, x, ldx, n_in, channels, y, ldy, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(PV_ERR_HIP, std::string("resample launch: ") + hipGetErrorString(e));
+    return PV_OK;
+}
+
+pv_status pv_pitch_reserve(pv_handle* h, int quality) {
+    if (!h) return fail(PV_ERR_ARG, "null handle");
+    if (h->mode != PV_MODE_STANDARD || h->effect != PV_TIME_SHIFT)
+        return fail(PV_ERR_UNSUPPORTED, "pv_pitch_reserve: STANDARD time-stretch handles only");
+    if (quality != 0 && quality != 1) return fail(PV_ERR_ARG, "pv_pitch_reserve: quality must be 0 (fast) or 1 (best)");
+    pv_resampler* rs = nullptr;
+    pv_status st = pv_resampler_create(h->hs, h->hop, quality, h->cfg.device, &rs);
+    if (st != PV_OK) return st;
+    DeviceGuard g(h->cfg.device);
+    // (rows of a multiple of 4 floats; a repeated reserve keeps the rows it has)
+    if (!h->d_pitch) {
+        const long long ld = (pv_output_length(h, std::max(h->cfg.max_frames, 1)) + 3) & ~3LL;
+        float* p = nullptr;
+        if (hipMalloc(&p, sizeof(float) * (size_t)ld * (size_t)std::max(h->cfg.max_channels, 1)) != hipSuccess) {
+            (void)hipGetLastError();
+            pv_resampler_destroy(rs);
+            return fail(PV_ERR_NOMEM, "pv_pitch_reserve: scratch rows");
+        }
+        h->d_pitch = p;
+        h->ld_pitch = ld;
+    }
+    if (h->pitch_rs) {
+        (void)hipDeviceSynchronize();  // calls in flight read the old table
+        pv_resampler_destroy(h->pitch_rs);
+    }
+    h->pitch_rs = rs;
+    return PV_OK;
+}
+
+long long pv_pitch_output_length(const pv_handle* h, int frames) {
+    if (!h) return 0;
+    return resample_length(h->hs, h->hop, pv_output_length(h, frames));
+}
+
+pv_status pv_pitch_process(pv_handle* h, const float* x, long long ldx, long long n_samples, int channels,
+                           int frames, pv_float2* spec, long long ld_spec, float* out, long long ldo,
+                           void* stream) {
+    pv_status st = check_common(h, channels, frames);
+    if (st != PV_OK) return st;
+    if (!h->pitch_rs) return fail(PV_ERR_ARG, "pv_pitch_process: call pv_pitch_reserve first");
+    DeviceGuard g(h->cfg.device);
+    ProfCall pc_(h);
+    hipStream_t s = (hipStream_t)stream;
+    // out hop = hop: no resampling, the time stretch writes `out`
+    if (!h->pitch_rs->d_tab)
+        return process_impl(h, x, ldx, n_samples, channels, frames, spec, ld_spec, out, ldo, s);
+    if (channels == 0 || frames == 0) return PV_OK;
+    if (!out) return fail(PV_ERR_ARG, "null out");
+    const long long n_mid = pv_output_length(h, frames);
+    if (channels > 1 && ldo < resample_length(h->pitch_rs->P, h->pitch_rs->Q, n_mid))
+        return fail(PV_ERR_ARG, "ldo < pv_pitch_output_length");
+    st = process_impl(h, x, ldx, n_samples, channels, frames, spec, ld_spec, h->d_pitch, h->ld_pitch, s);
+    if (st != PV_OK) return st;
+    PV_LAUNCH(h, KRES, s, resample_rows(h->pitch_rs, h->d_pitch, h->ld_pitch, n_mid, channels, out, ldo, s));
     return PV_OK;
 }
 

@@ -13,6 +13,10 @@
 //                                        time stretch only, not with --rt
 //     --formant ORDER                    formant-preserving pitch shift (pv_set_formant, lifter
 //                                        order 1 .. N/4): --mode std pitch shift only, not with --rt
+//     --pitch-resample fast|best         pitch shift by --scale as a time stretch followed by a
+//                                        band-limited resampling (pv_pitch_process): --mode std
+//                                        with effect t, every channel in one call; composes with
+//                                        --phase-lock; not with --rt
 //     --single-arg                       PhaseVocoder(N): periodic Hann, hop N/2 (phaseVocoder.h:46-78)
 //     --nan-faithful                     atanf(0/0) = NaN phases as the reference (kernel.cu:101-109)
 //     --timer                            print CudaPhase::timer() per call (main.cpp:238-241, 275-278)
@@ -78,6 +82,7 @@ int main(int argc, char** argv) {
     float scale = 1.0f;
     bool batched = false, single_arg = false, show_timer = false, rt = false, phase_lock = false;
     int formant = 0;
+    int pitch_resample = -1;  // --pitch-resample: quality preset (0 fast, 1 best)
     double ana_ms = 0.0, syn_ms = 0.0;
     pv_mode mode = PV_MODE_REF_COMPAT;
     std::vector<std::string> pos;
@@ -95,6 +100,14 @@ int main(int argc, char** argv) {
         else if (a == "--rt") rt = true;
         else if (a == "--phase-lock") phase_lock = true;
         else if (a == "--formant" && i + 1 < argc) formant = std::atoi(argv[++i]);
+        else if (a == "--pitch-resample" && i + 1 < argc) {
+            const std::string q = argv[++i];
+            if (q != "fast" && q != "best") {
+                std::fprintf(stderr, "err: --pitch-resample fast|best\n");
+                return 1;
+            }
+            pitch_resample = q == "best" ? 1 : 0;
+        }
         else pos.push_back(a);
     }
     if (pos.size() >= 1) in = pos[0];                                    // main.cpp:69-81
@@ -146,7 +159,18 @@ int main(int argc, char** argv) {
             return 1;
         }
     }
-    const int outLen = (int)(phase.timeScale * numSamples);
+    if (pitch_resample >= 0) {
+        if (rt) {
+            std::fprintf(stderr, "err: --pitch-resample: the real-time path has no such form\n");
+            return 1;
+        }
+        if (pv_pitch_reserve(phase.handle, pitch_resample) != PV_OK) {
+            std::fprintf(stderr, "err: --pitch-resample: %s\n", pv_last_error());
+            return 1;
+        }
+    }
+    // (the resampled stretch has the input's duration)
+    const int outLen = pitch_resample >= 0 ? numSamples : (int)(phase.timeScale * numSamples);
     std::vector<std::vector<float>> outFile(2, std::vector<float>(outLen > 0 ? outLen : 0, 0.f));
 
     float* d_input = nullptr;  // [channel][padN], zero padded
@@ -176,6 +200,26 @@ int main(int argc, char** argv) {
                 emitted.push_back(outBuf[j]);
             }
         }
+    } else if (pitch_resample >= 0) {
+        const long long olen = pv_pitch_output_length(phase.handle, frames);
+        float* d_out = nullptr;
+        HIPCHECK(hipMalloc((void**)&d_out, sizeof(float) * (size_t)std::max(olen, 1LL) * std::max(numChannels, 1)));
+        PhaseVocoder::checkCUDAErrori(pv_pitch_process(phase.handle, d_input, padN, numSamples, numChannels, frames,
+                                                       nullptr, 0, d_out, olen, nullptr),
+                                      "pv_pitch_process", __LINE__);
+        HIPCHECK(hipDeviceSynchronize());
+        std::vector<float> h((size_t)std::max(olen, 1LL));
+        const long long n_emit = std::min<long long>(olen, outLen);
+        // channel 0 to L, channel 1 (channel 0 of a mono file) to R
+        for (int c = 0; c < std::min(numChannels, 2); ++c) {
+            HIPCHECK(hipMemcpy(h.data(), d_out + (size_t)c * olen, sizeof(float) * olen, hipMemcpyDeviceToHost));
+            for (long long i = 0; i < n_emit; ++i) outFile[c][i] = h[i];
+            if (c == 0) {
+                emitted.assign(h.begin(), h.begin() + n_emit);
+                if (numChannels == 1) outFile[1] = outFile[0];
+            }
+        }
+        HIPCHECK(hipFree(d_out));
     } else if (batched) {
         const int S = phase.specStride();
         const long long olen = pv_output_length(phase.handle, frames);

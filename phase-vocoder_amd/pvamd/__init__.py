@@ -5,6 +5,7 @@ from .vocoder import (PITCH_SHIFT, REF_COMPAT, STANDARD, TIME_SHIFT,  # noqa: F4
                       PhaseVocoder)
 from .realtime import RealTimeVocoder  # noqa: F401
 from .harmonizer import Harmonizer  # noqa: F401
+from .resample import Resampler  # noqa: F401
 
 __all__ = ["PhaseVocoder", "PVError", "TIME_SHIFT", "PITCH_SHIFT", "REF_COMPAT", "STANDARD", "RealTimeVocoder", "Harmonizer",
-           "frame_count", "lib"]
+           "Resampler", "frame_count", "lib"]

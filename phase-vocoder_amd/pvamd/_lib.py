@@ -180,6 +180,20 @@ def lib():
     L.pv_harmonize.restype = i
     L.pv_harmonizer_set_formant.argtypes = [vp, i]
     L.pv_harmonizer_set_formant.restype = i
+    L.pv_resampler_create.argtypes = [i, i, i, i, ctypes.POINTER(vp)]
+    L.pv_resampler_create.restype = i
+    L.pv_resampler_destroy.argtypes = [vp]
+    L.pv_resampler_destroy.restype = None
+    L.pv_resample_length.argtypes = [vp, ll]
+    L.pv_resample_length.restype = ll
+    L.pv_resample.argtypes = [vp, vp, ll, ll, i, vp, ll, vp]
+    L.pv_resample.restype = i
+    L.pv_pitch_reserve.argtypes = [vp, i]
+    L.pv_pitch_reserve.restype = i
+    L.pv_pitch_output_length.argtypes = [vp, i]
+    L.pv_pitch_output_length.restype = ll
+    L.pv_pitch_process.argtypes = [vp, vp, ll, ll, i, i, vp, ll, vp, ll, vp]
+    L.pv_pitch_process.restype = i
     _lib = L
     return L
 

@@ -304,6 +304,40 @@ class PhaseVocoder:
                                       out.stride(0), self._stream(stream)), "pv_process")
         return out, spec
 
+    # -------------------------------------------------------------- pitch shift by resampling
+    def reserve_pitch(self, quality: int = 0):
+        """pv_pitch_reserve: build the handle's resampler (ratio outHopSize / hopSize; quality 0
+        fast, 1 best) and allocate the scratch rows of `pitch_process`.  STANDARD time-stretch
+        handles; a setup call (not capturable)."""
+        self._call(self._L.pv_pitch_reserve(self._h, int(quality)), "pv_pitch_reserve")
+
+    def pitch_output_length(self, frames: int) -> int:
+        return int(self._L.pv_pitch_output_length(self._h, int(frames)))
+
+    def pitch_process(self, x, frames: int | None = None, n_samples: int | None = None, spec=None,
+                      out=None, stream=None, spectrum: bool = True):
+        """pv_pitch_process: `process` (the time stretch, phase locking included) into the
+        handle's scratch rows, then the resampling by outHopSize / hopSize: the input's duration,
+        its pitch moved by that ratio.  Returns (out [C, pitch_output_length(frames)], spec), as
+        `process` does."""
+        torch = _torch()
+        x = self._as2d(x)
+        C, n = x.shape
+        n_samples = n if n_samples is None else n_samples
+        frames = self.num_frames(n_samples) if frames is None else frames
+        if not spectrum and spec is not None:
+            raise ValueError("spectrum=False with a spec buffer")
+        if spectrum and spec is None:
+            spec = self.alloc_spec(C, frames)
+        if out is None:
+            out = torch.empty((C, self.pitch_output_length(frames)), dtype=torch.float32,
+                              device=f"cuda:{self.device}")
+        self._call(self._L.pv_pitch_process(self._h, _ptr(x), x.stride(0), n_samples, C, frames,
+                                            _ptr(spec) if spec is not None else None,
+                                            spec.stride(0) // 2 if spec is not None else 0, _ptr(out),
+                                            out.stride(0), self._stream(stream)), "pv_pitch_process")
+        return out, spec
+
     def reserve_spectrum(self):
         """Allocate (once, zeroed) the handle's own spectrum rows that process(spectrum=False)
         uses on the split path, so that such calls can be captured into a graph."""
