@@ -77,7 +77,9 @@ extern "C" {
                                 pv_set_formant / pv_get_formant, pv_spectral_envelope,
                                 pv_harmonizer_set_formant, pv_resampler_* / pv_resample /
                                 pv_resample_length, pv_pitch_reserve / pv_pitch_process /
-                                pv_pitch_output_length) */
+                                pv_pitch_output_length, pv_rt_set_phase_lock /
+                                pv_rt_get_phase_lock, pv_rt_pitch_reserve / pv_rt_pitch_latency /
+                                pv_rt_pitch_push) */
 
 typedef struct pv_handle pv_handle;
 
@@ -277,7 +279,8 @@ pv_status pv_process(pv_handle* h, const float* x, long long ldx, long long n_sa
  * is turned off.
  * STANDARD + PV_TIME_SHIFT handles; otherwise PV_ERR_UNSUPPORTED.  Other values: PV_ERR_ARG.
  * A setup call (not capturable), ordered like the handle's compute calls: it takes effect
- * for the calls enqueued after it.  pv_rt and the harmoniser have no such switch. */
+ * for the calls enqueued after it.  pv_rt has its own switch (pv_rt_set_phase_lock); the
+ * harmoniser has none. */
 pv_status pv_set_phase_lock(pv_handle* h, int lock);
 int pv_get_phase_lock(const pv_handle* h);
 
@@ -359,7 +362,8 @@ pv_status pv_resample(pv_resampler* rs, const float* x, long long ldx, long long
  * REF_COMPAT or PV_PITCH_SHIFT handle: PV_ERR_UNSUPPORTED; out_hop / hop outside [1/4, 4]:
  * PV_ERR_UNSUPPORTED; bad quality: PV_ERR_ARG; pv_pitch_process before a successful
  * pv_pitch_reserve: PV_ERR_ARG; NULL handle: PV_ERR_ARG (0 from the length call).
- * pv_rt, the harmoniser and the stream segments have no such form. */
+ * pv_rt has a streaming form (pv_rt_pitch_push); the harmoniser and the stream segments have
+ * none. */
 pv_status pv_pitch_reserve(pv_handle* h, int quality);
 long long pv_pitch_output_length(const pv_handle* h, int frames);
 pv_status pv_pitch_process(pv_handle* h, const float* x, long long ldx, long long n_samples,
@@ -385,13 +389,61 @@ pv_status pv_rt_push(pv_rt* rt, const float* in, long long ldi, int nframes, flo
                      long long ldo, pv_float2* spec, long long ld_spec, void* stream);
 /* Capture one callback of `nframes` frames into a hipGraph: pinned host input -> device,
  * pv_rt_push, device -> pinned host output.  The pinned buffers are planar
- * [channels][nframes*hop] and [channels][nframes*out_hop] (pv_rt_host_buffers). */
+ * [channels][nframes*hop] and [channels][nframes*out_hop] (pv_rt_host_buffers); after
+ * pv_rt_pitch_reserve (below) the callback is pv_rt_pitch_push and the output buffer
+ * [channels][nframes*hop]. */
 pv_status pv_rt_capture(pv_rt* rt, int nframes);
 pv_status pv_rt_host_buffers(pv_rt* rt, float** host_in, float** host_out);
 /* One synchronous callback on the captured graph: copies `in` (host, planar, may be the
  * pinned buffer itself) into the pinned input, replays the graph, waits, copies the
  * result to `out` (host, may be the pinned output itself). */
 pv_status pv_rt_callback(pv_rt* rt, const float* in, float* out);
+
+/* Identity phase locking of the real-time time stretch: pv_set_phase_lock's semantics (above)
+ * on a pv_rt.  With locking on, pv_rt_push runs the locked form of its kernel and the emitted
+ * stream equals the locked pv_process() of the stream prefixed with N - hop zeros, frame for
+ * frame; the analysis, the spectrum rows and the unwrap decisions are unchanged and locking
+ * adds no stream state.  STANDARD + PV_TIME_SHIFT only, else PV_ERR_UNSUPPORTED; values other
+ * than 0, 1: PV_ERR_ARG.  A setup call: PV_ERR_ARG while a callback is captured (call it
+ * before pv_rt_capture). */
+pv_status pv_rt_set_phase_lock(pv_rt* rt, int lock);
+int pv_rt_get_phase_lock(const pv_rt* rt);
+
+/* Real-time pitch shift by time stretch and streaming resampling: a callback
+ * takes nframes*hop samples and gives nframes*hop pitch-shifted samples (ratio out_hop / hop)
+ * at a fixed latency.  It honours pv_rt_set_phase_lock.
+ *   S[n], n >= 0, is the stretched stream pv_rt_push would emit; S[n] = 0 for n < 0.
+ *   P/Q = out_hop / hop reduced; W, the filter h and the presets are pv_resampler_create's.
+ *   For every integer m, negative included:
+ *       y[m] = sum_{j = -W+1}^{W} S[i_m + j] h(j - r_m / Q),
+ *       i_m = floor(m P / Q) (toward -inf), r_m = m P mod Q in [0, Q).
+ *   The emitted stream is z[m'] = y[m' - D], m' >= 0, with D = floor(W Q / P) output samples
+ *   of latency (pv_rt_pitch_latency): the smallest delay at which every callback's outputs
+ *   read only stretched samples that callback or an earlier one has produced.
+ * A push of nframes frames consumes nframes*hop samples and emits exactly nframes*hop
+ * (out_hop Q / P = hop).  At out_hop = hop it is pv_rt_push bit for bit, with D = 0.  The stream
+ * does not depend on how it is cut into pushes (bit for bit), and no sample counter is kept: it
+ * can run for ever.  Accumulation is fp32 in the kernel's own tap order (tolerance bound, like
+ * pv_resample).
+ * pv_rt_pitch_reserve (a setup call: allocates, not capturable; PV_ERR_ARG while a callback is
+ * captured) builds the [Q][2W] coefficient table (fp64 on the host, rounded to fp32 once) and
+ * the per-channel scratch rows [H history | max_nframes*out_hop new stretched samples],
+ * H = 2W rounded up to a multiple of 4, zeroed; calling it again replaces quality and capacity
+ * and restarts the resampler's history.  pv_rt_reset zeroes the history too.
+ * pv_rt_pitch_push is pv_rt_push into the scratch rows, then one more launch (profile name
+ * rt_resample); same arguments as pv_rt_push, but out[c*ldo + i], i < nframes*hop.  No
+ * allocation, no synchronisation: capturable.  After a successful reserve pv_rt_capture
+ * captures pv_rt_pitch_push (nframes <= max_nframes, else PV_ERR_ARG) and the pinned output
+ * buffer is [channels][nframes*hop].
+ * PV_PITCH_SHIFT handle: PV_ERR_UNSUPPORTED; out_hop / hop outside [1/4, 4]:
+ * PV_ERR_UNSUPPORTED; bad quality, max_nframes <= 0 (or so large that max_nframes*hop*P
+ * leaves 31 bits): PV_ERR_ARG; pv_rt_pitch_push before a successful reserve or with
+ * nframes > max_nframes: PV_ERR_ARG; allocation failure: PV_ERR_NOMEM, and the feature stays
+ * off.  pv_rt_pitch_latency: 0 for a NULL rt or before a reserve. */
+pv_status pv_rt_pitch_reserve(pv_rt* rt, int quality, int max_nframes);
+int pv_rt_pitch_latency(const pv_rt* rt);
+pv_status pv_rt_pitch_push(pv_rt* rt, const float* in, long long ldi, int nframes, float* out,
+                           long long ldo, pv_float2* spec, long long ld_spec, void* stream);
 
 /* ---------------------------------------------------------------- harmoniser
  * K voices, voice k = PITCH_SHIFT by ratios[k] of the same input, all from ONE analysis

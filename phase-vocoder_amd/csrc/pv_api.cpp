@@ -39,11 +39,11 @@ pv_status fail(pv_status s, const std::string& msg) {
     } while (0)
 
 constexpr double kPi = 3.14159265358979323846;
-constexpr int kNumKernels = 12;
+constexpr int kNumKernels = 13;
 const char* kKernelNames[kNumKernels] = {"analysis", "runsum", "carry", "synthesis",
                                          "seam", "compat_analysis", "rt", "fused", "synthesis_locked",
-                                         "envelope", "synthesis_formant", "resample"};
-enum { KA = 0, KRS = 1, KC = 2, KS = 3, KSEAM = 4, KCA = 5, KRT = 6, KF = 7, KSL = 8, KENV = 9, KSF = 10, KRES = 11 };
+                                         "envelope", "synthesis_formant", "resample", "rt_resample"};
+enum { KA = 0, KRS = 1, KC = 2, KS = 3, KSEAM = 4, KCA = 5, KRT = 6, KF = 7, KSL = 8, KENV = 9, KSF = 10, KRES = 11, KRTR = 12 };
 
 bool is_pow2(long long v) { return v > 0 && (v & (v - 1)) == 0; }
 
@@ -1372,6 +1372,13 @@ struct pv_rt {
     float *d_hist = nullptr, *d_ola = nullptr, *d_phprev = nullptr;
     int* d_M = nullptr;
     unsigned* d_tcount = nullptr;
+    int phase_lock = 0;  // pv_rt_set_phase_lock: k_rt in kModeLocked
+    // pv_rt_pitch_reserve: the streaming resampler of pv_rt_pitch_push (P = out hop, Q = hop,
+    // reduced).  d_prow: [channels][ld_prow] scratch rows [H history | max_nframes * out hop new
+    // stretched samples]; d_ptab: [Q][2W] coefficients (nullptr at ratio 1: no resampling)
+    int pitch_on = 0, pitch_P = 1, pitch_Q = 1, pitch_W = 0, pitch_H = 0, pitch_D = 0, pitch_max = 0;
+    float *d_prow = nullptr, *d_ptab = nullptr;
+    long long ld_prow = 0;
     // captured callback
     int g_nframes = 0;
     float *h_in = nullptr, *h_out = nullptr, *d_in = nullptr, *d_out = nullptr;
@@ -1397,6 +1404,14 @@ void rt_release_graph(pv_rt* rt) {
     rt->h_in = rt->h_out = rt->d_in = rt->d_out = nullptr;
     rt->g_nframes = 0;
 }
+// samples per frame a callback emits: hop once pv_rt_pitch_reserve has succeeded, else out hop
+int rt_out_hop(const pv_rt* rt) { return rt->pitch_on ? rt->h->hop : rt->h->hs; }
+// what a callback runs: pv_rt_pitch_push after pv_rt_pitch_reserve, else pv_rt_push
+pv_status rt_callback_push(pv_rt* rt, const float* in, long long ldi, int nframes, float* out, long long ldo,
+                           hipStream_t s) {
+    return rt->pitch_on ? pv_rt_pitch_push(rt, in, ldi, nframes, out, ldo, nullptr, 0, s)
+                        : pv_rt_push(rt, in, ldi, nframes, out, ldo, nullptr, 0, s);
+}
 }  // namespace
 
 extern "C" {
@@ -1407,7 +1422,7 @@ void pv_rt_destroy(pv_rt* rt) {
         DeviceGuard g(rt->h->cfg.device);
         rt_release_graph(rt);
         if (rt->g_stream) (void)hipStreamDestroy(rt->g_stream);
-        void* ptrs[] = {rt->d_hist, rt->d_ola, rt->d_phprev, rt->d_M, rt->d_tcount};
+        void* ptrs[] = {rt->d_hist, rt->d_ola, rt->d_phprev, rt->d_M, rt->d_tcount, rt->d_prow, rt->d_ptab};
         for (void* p : ptrs)
             if (p) (void)hipFree(p);
         pv_destroy(rt->h);
@@ -1425,6 +1440,7 @@ pv_status pv_rt_reset(pv_rt* rt, void* stream) {
     PV_HIP(hipMemsetAsync(rt->d_phprev, 0, sizeof(float) * C * BP, s));
     PV_HIP(hipMemsetAsync(rt->d_M, 0, sizeof(int) * C * BP, s));
     PV_HIP(hipMemsetAsync(rt->d_tcount, 0, sizeof(unsigned) * C, s));
+    if (rt->d_prow) PV_HIP(hipMemsetAsync(rt->d_prow, 0, sizeof(float) * C * (size_t)rt->ld_prow, s));
     return PV_OK;
 }
 
@@ -1522,23 +1538,25 @@ pv_status pv_rt_push(pv_rt* rt, const float* in, long long ldi, int nframes, flo
     p.inv_q = h->inv_q;
     hipStream_t s = (hipStream_t)stream;
     prof_tick(h);  // one public call: the profile stride counts pv_rt_push calls too
-    PV_LAUNCH(h, KRT, s, pv::launch_rt(h->L_syn, h->pitch ? 2 : 0, p, s));
+    PV_LAUNCH(h, KRT, s, pv::launch_rt(h->L_syn, h->pitch ? 2 : rt->phase_lock ? pv::kRtModeLocked : 0, p, s));
     return PV_OK;
 }
 
 pv_status pv_rt_capture(pv_rt* rt, int nframes) {
     if (!rt) return fail(PV_ERR_ARG, "null rt");
     if (nframes <= 0) return fail(PV_ERR_ARG, "nframes must be > 0");
+    if (rt->pitch_on && nframes > rt->pitch_max)
+        return fail(PV_ERR_ARG, "pv_rt_capture: nframes > max_nframes of pv_rt_pitch_reserve");
     pv_handle* h = rt->h;
     DeviceGuard g(h->cfg.device);
     rt_release_graph(rt);
     if (!rt->g_stream) PV_HIP(hipStreamCreateWithFlags(&rt->g_stream, hipStreamNonBlocking));
     const size_t C = (size_t)rt->channels;
-    const size_t ni = (size_t)nframes * h->hop, no = (size_t)nframes * h->hs;
+    const size_t ni = (size_t)nframes * h->hop, no = (size_t)nframes * rt_out_hop(rt);
     // pinned, device-mapped host buffers: the captured kernel reads the callback's input
     // and writes its output in place over the bus (zero-copy: the graph is one kernel
-    // node, no copy nodes); if the runtime cannot map them, the graph copies H2D / D2H
-    // around the kernel instead
+    // node, two after pv_rt_pitch_reserve, no copy nodes); if the runtime cannot map them,
+    // the graph copies H2D / D2H around the kernels instead
     PV_HIP(hipHostMalloc((void**)&rt->h_in, sizeof(float) * C * ni, hipHostMallocMapped));
     PV_HIP(hipHostMalloc((void**)&rt->h_out, sizeof(float) * C * no, hipHostMallocMapped));
     std::memset(rt->h_in, 0, sizeof(float) * C * ni);
@@ -1557,12 +1575,12 @@ pv_status pv_rt_capture(pv_rt* rt, int nframes) {
     PV_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
     pv_status st = PV_OK;
     if (zero_copy) {
-        st = pv_rt_push(rt, m_in, (long long)ni, nframes, m_out, (long long)no, nullptr, 0, s);
+        st = rt_callback_push(rt, m_in, (long long)ni, nframes, m_out, (long long)no, s);
     } else {
         if (hipMemcpyAsync(rt->d_in, rt->h_in, sizeof(float) * C * ni, hipMemcpyHostToDevice, s) != hipSuccess)
             st = fail(PV_ERR_HIP, "pv_rt_capture: H2D capture failed");
         if (st == PV_OK)
-            st = pv_rt_push(rt, rt->d_in, (long long)ni, nframes, rt->d_out, (long long)no, nullptr, 0, s);
+            st = rt_callback_push(rt, rt->d_in, (long long)ni, nframes, rt->d_out, (long long)no, s);
         if (st == PV_OK &&
             hipMemcpyAsync(rt->h_out, rt->d_out, sizeof(float) * C * no, hipMemcpyDeviceToHost, s) != hipSuccess)
             st = fail(PV_ERR_HIP, "pv_rt_capture: D2H capture failed");
@@ -1597,11 +1615,11 @@ pv_status pv_rt_callback(pv_rt* rt, const float* in, float* out) {
     pv_handle* h = rt->h;
     DeviceGuard g(h->cfg.device);
     const size_t C = (size_t)rt->channels;
-    const size_t ni = (size_t)rt->g_nframes * h->hop, no = (size_t)rt->g_nframes * h->hs;
+    const size_t ni = (size_t)rt->g_nframes * h->hop, no = (size_t)rt->g_nframes * rt_out_hop(rt);
     if (in && in != rt->h_in) std::memcpy(rt->h_in, in, sizeof(float) * C * ni);  // main.cpp:49
     if (rt->direct) {
-        pv_status st = pv_rt_push(rt, rt->m_in, (long long)ni, rt->g_nframes, rt->m_out, (long long)no, nullptr, 0,
-                                  rt->g_stream);
+        pv_status st = rt_callback_push(rt, rt->m_in, (long long)ni, rt->g_nframes, rt->m_out, (long long)no,
+                                        rt->g_stream);
         if (st != PV_OK) return st;
     } else {
         PV_HIP(hipGraphLaunch(rt->exec, rt->g_stream));
@@ -1784,28 +1802,38 @@ long long gcd_ll(long long a, long long b) {
     return a;
 }
 
-// the eight alignments of the Q x 2W coefficient table (pv_resample.hpp ResampleParams::tab),
-// fp64 rounded to fp32 once
-void resample_table(int P, int Q, int quality, const pv::ResamplePlan& plan, std::vector<float>& tab) {
+// half width W = ceil(Z / s) of the reduced ratio's filter (include/pv.h)
+int resample_half_width(int P, int Q, int quality) {
+    const double s = kResamplePresets[quality][1] * std::min(1.0, (double)Q / (double)P);
+    return (int)std::ceil(kResamplePresets[quality][0] / s);
+}
+
+// the coefficients of phase r: row[t] = h(t - W + 1 - r / Q), t < 2W, fp64 rounded to fp32 once
+void resample_row(int P, int Q, int quality, int W, int r, float* row) {
     const double Z = kResamplePresets[quality][0], rolloff = kResamplePresets[quality][1],
                  beta = kResamplePresets[quality][2];
     const double s = rolloff * std::min(1.0, (double)Q / (double)P);
     const double i0b = bessel_i0(beta);
+    for (int t = 0; t < 2 * W; ++t) {
+        const double tau = (double)(t - W + 1) - (double)r / (double)Q;
+        const double u = s * tau / Z;
+        double v = 0.0;
+        if (std::fabs(u) < 1.0) {
+            const double a = kPi * s * tau;
+            const double sinc = (a == 0.0) ? 1.0 : std::sin(a) / a;
+            v = s * sinc * bessel_i0(beta * std::sqrt(1.0 - u * u)) / i0b;
+        }
+        row[t] = (float)v;
+    }
+}
+
+// the eight alignments of the Q x 2W coefficient table (pv_resample.hpp ResampleParams::tab)
+void resample_table(int P, int Q, int quality, const pv::ResamplePlan& plan, std::vector<float>& tab) {
     const int W = plan.W, NC = plan.NC;
     std::vector<float> row(2 * W);
     tab.assign((size_t)8 * Q * NC * 4, 0.0f);
     for (int r = 0; r < Q; ++r) {
-        for (int t = 0; t < 2 * W; ++t) {
-            const double tau = (double)(t - W + 1) - (double)r / (double)Q;
-            const double u = s * tau / Z;
-            double v = 0.0;
-            if (std::fabs(u) < 1.0) {
-                const double a = kPi * s * tau;
-                const double sinc = (a == 0.0) ? 1.0 : std::sin(a) / a;
-                v = s * sinc * bessel_i0(beta * std::sqrt(1.0 - u * u)) / i0b;
-            }
-            row[t] = (float)v;
-        }
+        resample_row(P, Q, quality, W, r, row.data());
         for (int off = 0; off < 8; ++off) {
             float* dst = tab.data() + ((size_t)off * Q + r) * NC * 4;
             for (int t = 0; t < 2 * W; ++t) dst[t + off] = row[t];
@@ -1859,8 +1887,7 @@ pv_status pv_resampler_create(int p, int q, int quality, int device, pv_resample
     rs->quality = quality;
     rs->device = device;
     if (P != Q) {
-        const double s = kResamplePresets[quality][1] * std::min(1.0, (double)Q / (double)P);
-        const int W = (int)std::ceil(kResamplePresets[quality][0] / s);
+        const int W = resample_half_width(rs->P, rs->Q, quality);
         if (!pv::resample_plan(rs->P, rs->Q, W, &rs->plan)) {
             delete rs;
             return fail(PV_ERR_UNSUPPORTED, "pv_resampler_create: no tile plan for this ratio");
@@ -1967,6 +1994,113 @@ pv_status pv_pitch_process(pv_handle* h, const float* x, long long ldx, long lon
     st = process_impl(h, x, ldx, n_samples, channels, frames, spec, ld_spec, h->d_pitch, h->ld_pitch, s);
     if (st != PV_OK) return st;
     PV_LAUNCH(h, KRES, s, resample_rows(h->pitch_rs, h->d_pitch, h->ld_pitch, n_mid, channels, out, ldo, s));
+    return PV_OK;
+}
+
+// ---- real-time pitch shift: the locked stretch and the streaming resampler
+pv_status pv_rt_set_phase_lock(pv_rt* rt, int lock) {
+    if (!rt) return fail(PV_ERR_ARG, "null rt");
+    if (lock != 0 && lock != 1) return fail(PV_ERR_ARG, "pv_rt_set_phase_lock: lock must be 0 or 1");
+    if (rt->h->mode != PV_MODE_STANDARD || rt->h->effect != PV_TIME_SHIFT)
+        return fail(PV_ERR_UNSUPPORTED, "pv_rt_set_phase_lock: STANDARD time-stretch handles only");
+    if (rt->exec) return fail(PV_ERR_ARG, "pv_rt_set_phase_lock: a callback is captured (call it before pv_rt_capture)");
+    rt->phase_lock = lock;
+    return PV_OK;
+}
+
+int pv_rt_get_phase_lock(const pv_rt* rt) { return rt ? rt->phase_lock : 0; }
+
+pv_status pv_rt_pitch_reserve(pv_rt* rt, int quality, int max_nframes) {
+    if (!rt) return fail(PV_ERR_ARG, "null rt");
+    pv_handle* h = rt->h;
+    if (h->mode != PV_MODE_STANDARD || h->effect != PV_TIME_SHIFT)
+        return fail(PV_ERR_UNSUPPORTED, "pv_rt_pitch_reserve: STANDARD time-stretch handles only");
+    if (quality != 0 && quality != 1) return fail(PV_ERR_ARG, "pv_rt_pitch_reserve: quality must be 0 (fast) or 1 (best)");
+    if (max_nframes <= 0) return fail(PV_ERR_ARG, "pv_rt_pitch_reserve: max_nframes must be > 0");
+    if (rt->exec) return fail(PV_ERR_ARG, "pv_rt_pitch_reserve: a callback is captured (call it before pv_rt_capture)");
+    const long long g = gcd_ll(h->hs, h->hop);
+    const long long P = h->hs / g, Q = h->hop / g;
+    if (P > 4 * Q || Q > 4 * P) return fail(PV_ERR_UNSUPPORTED, "pv_rt_pitch_reserve: out_hop / hop in [1/4, 4]");
+    const int W = (P == Q) ? 0 : resample_half_width((int)P, (int)Q, quality);
+    const int H = (2 * W + 3) & ~3;
+    const long long D = (P == Q) ? 0 : (long long)W * Q / P;
+    // the kernel's dividend (u P + W Q - D P, u < max_nframes * hop) in 32 bits
+    if ((long long)max_nframes * h->hop * P + (long long)W * Q > 0x7fffffffLL)
+        return fail(PV_ERR_ARG, "pv_rt_pitch_reserve: max_nframes too large");
+    DeviceGuard dg(h->cfg.device);
+    float *row = nullptr, *tab = nullptr;
+    long long ld = 0;
+    if (P != Q) {
+        std::vector<float> t((size_t)Q * 2 * W);
+        for (int r = 0; r < (int)Q; ++r) resample_row((int)P, (int)Q, quality, W, r, t.data() + (size_t)r * 2 * W);
+        ld = ((long long)H + (long long)max_nframes * h->hs + 3) & ~3LL;
+        const size_t row_bytes = sizeof(float) * (size_t)ld * (size_t)rt->channels;
+        if (hipMalloc((void**)&row, row_bytes) != hipSuccess ||
+            hipMalloc((void**)&tab, sizeof(float) * t.size()) != hipSuccess) {
+            (void)hipGetLastError();
+            if (row) (void)hipFree(row);
+            return fail(PV_ERR_NOMEM, "pv_rt_pitch_reserve: scratch rows / coefficient table");
+        }
+        if (hipMemset(row, 0, row_bytes) != hipSuccess ||
+            hipMemcpy(tab, t.data(), sizeof(float) * t.size(), hipMemcpyHostToDevice) != hipSuccess ||
+            hipDeviceSynchronize() != hipSuccess) {
+            (void)hipFree(row);
+            (void)hipFree(tab);
+            return fail(PV_ERR_HIP, "pv_rt_pitch_reserve: uploading the coefficient table");
+        }
+    }
+    // a repeated reserve replaces the quality and the capacity; the resampler's history restarts
+    if (rt->d_prow || rt->d_ptab) {
+        (void)hipDeviceSynchronize();  // pushes in flight read the old rows and table
+        if (rt->d_prow) (void)hipFree(rt->d_prow);
+        if (rt->d_ptab) (void)hipFree(rt->d_ptab);
+    }
+    rt->d_prow = row;
+    rt->d_ptab = tab;
+    rt->ld_prow = ld;
+    rt->pitch_P = (int)P;
+    rt->pitch_Q = (int)Q;
+    rt->pitch_W = W;
+    rt->pitch_H = H;
+    rt->pitch_D = (int)D;
+    rt->pitch_max = max_nframes;
+    rt->pitch_on = 1;
+    return PV_OK;
+}
+
+int pv_rt_pitch_latency(const pv_rt* rt) { return (rt && rt->pitch_on) ? rt->pitch_D : 0; }
+
+pv_status pv_rt_pitch_push(pv_rt* rt, const float* in, long long ldi, int nframes, float* out, long long ldo,
+                           pv_float2* spec, long long ld_spec, void* stream) {
+    if (!rt) return fail(PV_ERR_ARG, "null rt");
+    if (!rt->pitch_on) return fail(PV_ERR_ARG, "pv_rt_pitch_push: call pv_rt_pitch_reserve first");
+    if (nframes > rt->pitch_max) return fail(PV_ERR_ARG, "pv_rt_pitch_push: nframes > max_nframes of pv_rt_pitch_reserve");
+    // out hop = hop: no resampling, the stretch writes `out`
+    if (!rt->d_ptab) return pv_rt_push(rt, in, ldi, nframes, out, ldo, spec, ld_spec, stream);
+    if (nframes < 0) return fail(PV_ERR_ARG, "negative nframes");
+    if (nframes == 0) return PV_OK;
+    pv_handle* h = rt->h;
+    if (!in || !out) return fail(PV_ERR_ARG, "null in/out");
+    if (rt->channels > 1 && ldo < (long long)nframes * h->hop) return fail(PV_ERR_ARG, "ldo smaller than one callback");
+    pv_status st = pv_rt_push(rt, in, ldi, nframes, rt->d_prow + rt->pitch_H, rt->ld_prow, spec, ld_spec, stream);
+    if (st != PV_OK) return st;
+    DeviceGuard g(h->cfg.device);
+    pv::RtResampleParams p{};
+    p.row = rt->d_prow;
+    p.ld_row = rt->ld_prow;
+    p.out = out;
+    p.ldo = ldo;
+    p.tab = rt->d_ptab;
+    p.channels = rt->channels;
+    p.n_new = nframes * h->hs;
+    p.n_out = nframes * h->hop;
+    p.P = rt->pitch_P;
+    p.Q = rt->pitch_Q;
+    p.W = rt->pitch_W;
+    p.H = rt->pitch_H;
+    p.off = (unsigned)((long long)rt->pitch_W * rt->pitch_Q - (long long)rt->pitch_D * rt->pitch_P);
+    hipStream_t s = (hipStream_t)stream;
+    PV_LAUNCH(h, KRTR, s, pv::launch_rt_resample(p, s));
     return PV_OK;
 }
 

@@ -206,6 +206,23 @@ struct RtParams {
     float inv_q;
 };
 
+// streaming resampler of the real-time pitch shift (pv_rt_pitch.hip): one launch per callback
+// after k_rt, a workgroup per channel.  row[c * ld_row ..]: [H history | n_new stretched samples]
+// (k_rt wrote the new ones at row + H); output u < n_out reads the 2W samples from
+// row[H - 2W + 1 + (u P + off) / Q] on with the coefficients tab[((u P + off) mod Q) * 2W ..],
+// then the last H samples of the row move to its front.
+struct RtResampleParams {
+    float* row;
+    long long ld_row;
+    float* out;                        // [C][n_out] (row stride ldo)
+    long long ldo;
+    const float* tab;                  // [Q][2W], c[r][t] = h(t - W + 1 - r / Q)
+    int channels;
+    int n_new, n_out;                  // nframes * out hop, nframes * hop
+    int P, Q, W, H;
+    unsigned off;                      // W Q - D P >= 0; (n_out - 1) P + off < 2^31
+};
+
 // harmoniser mix: dst[c][i] = sum_k gain[k] * src[k][c][i]
 struct MixParams {
     const float* src;
@@ -244,8 +261,11 @@ size_t synthesis_lds_bytes(int L, int hs);
 hipError_t launch_fft(int n, int inverse, const float2* in, float2* out, const float2* tw, int batch,
                       hipStream_t s);
 hipError_t launch_mix(const MixParams& p, hipStream_t s);
+// mode: 0 STANDARD stretch, 2 STANDARD pitch, kRtModeLocked the stretch with identity phase locking
+constexpr int kRtModeLocked = 6;  // (= kModeLocked, pv_lock.hpp)
 hipError_t launch_rt(int L, int mode, const RtParams& p, hipStream_t s);
 size_t rt_lds_bytes(int L);
+hipError_t launch_rt_resample(const RtResampleParams& p, hipStream_t s);
 hipError_t launch_window_gain(const float* win, float* dwin, float* gain, int n, hipStream_t s);
 hipError_t launch_overlap_test(const float* in, const float* win, const float* back, float* out,
                                int n, int hop, hipStream_t s);

@@ -15,6 +15,12 @@
 // emitting out_hop final samples.  The per-frame arithmetic is the batched path's
 // (pv_frame.hpp), so the stream equals pv_process() over the stream prefixed with
 // N - hop zeros, frame for frame (tests/test_gpu_rt.py).
+//
+// MODE kModeLocked (pv_rt_set_phase_lock): the stretch with identity phase locking, synth_frame's
+// locked step as in k_synthesis_locked (pv_locked.hip).  Its theta scratch is the wave's FFT
+// tile, which is free between the analysis split (read from registers) and the inverse FFT.
+// Locking adds no stream state.  Instantiations of their own: the k_rt<L, 0|2, ..> kernels keep
+// their code.
 #include "pv_frame.hpp"
 #include "pv_kernels.h"
 
@@ -53,6 +59,7 @@ __global__ __launch_bounds__(256) void k_rt(RtParams p) {
     constexpr int B = R_::B;
     constexpr int W = R_::W;
     constexpr int SPW = N / 64;
+    static_assert(MODE != kModeLocked || 2 * R_::TILE >= L + 2, "theta scratch of the locked step: L + 2 floats");
     extern __shared__ __attribute__((aligned(16))) float rsm[];
     float2* twl = reinterpret_cast<float2*>(rsm + R_::O_TW);
     float2* twsl = reinterpret_cast<float2*>(rsm + R_::O_TWS);
@@ -202,13 +209,16 @@ size_t rt_lds_bytes(int L) {
 
 int rt_waves_per_group(int L) { return L <= 512 ? 4 : 2; }
 
-// mode: 0 STANDARD stretch, 2 STANDARD pitch
+// mode: 0 STANDARD stretch, 2 STANDARD pitch, kModeLocked the stretch with phase locking
+static_assert(kRtModeLocked == kModeLocked, "launch_rt's locked mode is synth_frame's");
 hipError_t launch_rt(int L, int mode, const RtParams& p, hipStream_t s) {
     const int W = rt_waves_per_group(L);
     dim3 grid((p.channels + W - 1) / W), block(64 * W);
     const bool qp = p.q_pow2 && p.q <= (1ull << 24);
 #define PV_RT_L(LL_)                                                                              \
-    if (mode == 2 && qp) hipLaunchKernelGGL((k_rt<LL_, 2, true>), grid, block, RtGeo<LL_>::BYTES, s, p); \
+    if (mode == kModeLocked && qp) hipLaunchKernelGGL((k_rt<LL_, kModeLocked, true>), grid, block, RtGeo<LL_>::BYTES, s, p); \
+    else if (mode == kModeLocked) hipLaunchKernelGGL((k_rt<LL_, kModeLocked, false>), grid, block, RtGeo<LL_>::BYTES, s, p); \
+    else if (mode == 2 && qp) hipLaunchKernelGGL((k_rt<LL_, 2, true>), grid, block, RtGeo<LL_>::BYTES, s, p); \
     else if (mode == 2) hipLaunchKernelGGL((k_rt<LL_, 2, false>), grid, block, RtGeo<LL_>::BYTES, s, p); \
     else if (qp) hipLaunchKernelGGL((k_rt<LL_, 0, true>), grid, block, RtGeo<LL_>::BYTES, s, p);   \
     else hipLaunchKernelGGL((k_rt<LL_, 0, false>), grid, block, RtGeo<LL_>::BYTES, s, p);

@@ -168,6 +168,16 @@ def lib():
     L.pv_rt_host_buffers.restype = i
     L.pv_rt_callback.argtypes = [vp, vp, vp]
     L.pv_rt_callback.restype = i
+    L.pv_rt_set_phase_lock.argtypes = [vp, i]
+    L.pv_rt_set_phase_lock.restype = i
+    L.pv_rt_get_phase_lock.argtypes = [vp]
+    L.pv_rt_get_phase_lock.restype = i
+    L.pv_rt_pitch_reserve.argtypes = [vp, i, i]
+    L.pv_rt_pitch_reserve.restype = i
+    L.pv_rt_pitch_latency.argtypes = [vp]
+    L.pv_rt_pitch_latency.restype = i
+    L.pv_rt_pitch_push.argtypes = [vp, vp, ll, i, vp, ll, vp, ll, vp]
+    L.pv_rt_pitch_push.restype = i
     L.pv_fft_c2c.argtypes = [vp, vp, i, i, i, vp]
     L.pv_fft_c2c.restype = i
     L.pv_harmonizer_create.argtypes = [ctypes.POINTER(pv_config), ctypes.POINTER(ctypes.c_float), i,

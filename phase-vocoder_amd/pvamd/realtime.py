@@ -6,6 +6,11 @@ that looks back at `prev_input` / `prev_mag_phase` / `prev_output`
 (src/phaseVocoder.h:16-31, README.md:46-50).  `RealTimeVocoder` keeps that shape: state
 lives on the device between callbacks, one callback is one hipGraph replay
 (`capture` + `callback`), or one `push` on a caller's stream.
+
+A time-stretch vocoder can also shift the pitch live: `set_phase_lock` turns identity phase
+locking on, `reserve_pitch` adds the streaming resampler, and `pitch_push` (or the captured
+callback) then takes nframes*hopSize samples and gives nframes*hopSize shifted ones,
+`pitch_latency` output samples late.
 """
 from __future__ import annotations
 
@@ -19,7 +24,7 @@ from .vocoder import PITCH_SHIFT, TIME_SHIFT, _ptr, _torch  # noqa: F401
 
 class RealTimeVocoder:
     def __init__(self, samples: int, effect: str = PITCH_SHIFT, scaleFactor: float = 1.0,
-                 hop: int = 4, *, channels: int = 1, device: int = 0):
+                 hop: int = 4, *, channels: int = 1, device: int = 0, phase_lock: bool = False):
         eff = effect if isinstance(effect, int) else ord(effect)
         cfg = _lib.config(samples, hop, eff, scaleFactor, _lib.PV_MODE_STANDARD, channels, 1, device)
         self._L = _lib.lib()
@@ -34,6 +39,9 @@ class RealTimeVocoder:
         self.spec_bins = self.nSamps // 2 + 1
         self.spec_stride = (self.spec_bins + 7) & ~7
         self._graph_frames = 0
+        self._pitch = False
+        if phase_lock:
+            self.set_phase_lock(True)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -69,6 +77,42 @@ class RealTimeVocoder:
                                       _ptr(spec), lds, self._stream(stream)), "pv_rt_push")
         return out
 
+    # ---------------------------------------------------------- locked stretch, pitch shift
+    def set_phase_lock(self, lock: bool = True):
+        """pv_rt_set_phase_lock: identity phase locking of the time stretch (time-stretch
+        vocoders only; before `capture`)."""
+        _lib.check(self._L.pv_rt_set_phase_lock(self._h, 1 if lock else 0), "pv_rt_set_phase_lock")
+
+    @property
+    def phase_lock(self) -> bool:
+        return bool(self._L.pv_rt_get_phase_lock(self._h))
+
+    def reserve_pitch(self, quality: int = 0, max_frames: int = 1):
+        """pv_rt_pitch_reserve: the streaming resampler of `pitch_push` (quality 0 fast, 1 best)
+        for pushes of up to max_frames frames; time-stretch vocoders only, before `capture`."""
+        _lib.check(self._L.pv_rt_pitch_reserve(self._h, int(quality), int(max_frames)), "pv_rt_pitch_reserve")
+        self._pitch = True
+
+    @property
+    def pitch_latency(self) -> int:
+        """output samples by which `pitch_push`'s stream is delayed (0 before `reserve_pitch`)"""
+        return int(self._L.pv_rt_pitch_latency(self._h))
+
+    def pitch_push(self, x, out=None, spec=None, stream=None):
+        """x: [C, nframes*hop] CUDA float32 -> out [C, nframes*hop], shifted in pitch by
+        outHop / hop (device, async)."""
+        torch = _torch()
+        x = x.unsqueeze(0) if x.dim() == 1 else x
+        C, n = x.shape
+        assert C == self.channels and n % self.hopSize == 0 and x.stride(-1) == 1
+        nf = n // self.hopSize
+        if out is None:
+            out = torch.empty((C, n), dtype=torch.float32, device=x.device)
+        lds = 0 if spec is None else spec.stride(0) // 2
+        _lib.check(self._L.pv_rt_pitch_push(self._h, _ptr(x), x.stride(0), nf, _ptr(out), out.stride(0),
+                                            _ptr(spec), lds, self._stream(stream)), "pv_rt_pitch_push")
+        return out
+
     # ---------------------------------------------------------- captured callback
     def capture(self, nframes: int = 1):
         _lib.check(self._L.pv_rt_capture(self._h, int(nframes)), "pv_rt_capture")
@@ -77,14 +121,16 @@ class RealTimeVocoder:
         fo = ctypes.POINTER(ctypes.c_float)()
         _lib.check(self._L.pv_rt_host_buffers(self._h, ctypes.byref(fi), ctypes.byref(fo)),
                    "pv_rt_host_buffers")
-        ni, no = nframes * self.hopSize, nframes * self.outHopSize
+        # (after reserve_pitch the callback is pitch_push: nframes * hop samples out)
+        ni, no = nframes * self.hopSize, nframes * (self.hopSize if self._pitch else self.outHopSize)
         # zero-copy numpy views of the pinned callback buffers
         self.host_in = np.ctypeslib.as_array(fi, shape=(self.channels, ni))
         self.host_out = np.ctypeslib.as_array(fo, shape=(self.channels, no))
 
     def callback(self, x: np.ndarray | None = None) -> np.ndarray:
         """One synchronous callback: x (host [C, nframes*hop], or None when host_in was
-        filled in place) -> host_out view [C, nframes*outHop]."""
+        filled in place) -> host_out view [C, nframes*outHop] ([C, nframes*hop] after
+        `reserve_pitch`)."""
         src = None
         if x is not None:
             x = np.ascontiguousarray(x, dtype=np.float32)
