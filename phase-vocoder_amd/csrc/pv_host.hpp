@@ -1,0 +1,282 @@
+// pv_host.hpp — what the host translation units of libpv share (pv_api*.cpp): error
+// reporting, the device-memory owner, the handle structs, the per-launch profiler and the
+// launch sequences one component calls of another.  Nothing here is part of the C-ABI.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "../../include/pv.h"
+#include "pv_kernels.h"
+#include "pv_resample.hpp"
+#include "pv_tables.hpp"
+
+#pragma GCC visibility push(hidden)
+namespace pvhost {
+
+using namespace pvtab;
+
+// records the calling thread's pv_last_error() (pv_api.cpp) and returns s
+pv_status fail(pv_status s, const std::string& msg);
+
+#define PV_HIP(expr)                                                                    \
+    do {                                                                                \
+        hipError_t e_ = (expr);                                                         \
+        if (e_ != hipSuccess)                                                           \
+            return fail(e_ == hipErrorOutOfMemory ? PV_ERR_NOMEM : PV_ERR_HIP,          \
+                        std::string(#expr) + ": " + hipGetErrorString(e_));             \
+    } while (0)
+
+// kernel ids of the per-launch profile and their names (pv_profile_read), index for index
+enum { KA, KRS, KC, KS, KSEAM, KCA, KRT, KF, KSL, KENV, KSF, KRES, KRTR, kNumKernels };
+inline constexpr const char* kKernelNames[] = {"analysis", "runsum", "carry", "synthesis", "seam",
+                                               "compat_analysis", "rt", "fused", "synthesis_locked",
+                                               "envelope", "synthesis_formant", "resample", "rt_resample"};
+static_assert(sizeof(kKernelNames) / sizeof(kKernelNames[0]) == kNumKernels, "one name per kernel id");
+
+// Move-only owner of one hipMalloc (Pinned: hipHostMalloc, device-mapped) allocation.  Converts
+// to the raw pointer kernels receive; freed on reset() or destruction, on the device that is
+// current then (callers hold a DeviceGuard).
+template <typename T, bool Pinned = false>
+struct DevBuf {
+    T* p = nullptr;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            reset();
+            p = o.p;
+            o.p = nullptr;
+        }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    operator T*() const { return p; }
+    void reset() {
+        if (p) (void)(Pinned ? hipHostFree(p) : hipFree(p));
+        p = nullptr;
+    }
+    // n elements (at least one byte is allocated); the earlier allocation is released first
+    hipError_t alloc(size_t n) {
+        reset();
+        const size_t bytes = sizeof(T) * (n ? n : 1);
+        hipError_t e = Pinned ? hipHostMalloc((void**)&p, bytes, hipHostMallocMapped) : hipMalloc((void**)&p, bytes);
+        if (e != hipSuccess) p = nullptr;
+        return e;
+    }
+    hipError_t alloc_zero(size_t n) {
+        hipError_t e = alloc(n);
+        return e != hipSuccess ? e : hipMemset(p, 0, sizeof(T) * (n ? n : 1));
+    }
+    hipError_t upload(const T* src, size_t n) {
+        hipError_t e = alloc(n);
+        return (e != hipSuccess || n == 0) ? e : hipMemcpy(p, src, sizeof(T) * n, hipMemcpyHostToDevice);
+    }
+};
+
+struct DeviceGuard {
+    int prev = -1;
+    explicit DeviceGuard(int dev) {
+        if (hipGetDevice(&prev) == hipSuccess && prev != dev) (void)hipSetDevice(dev);
+        else prev = -1;
+    }
+    ~DeviceGuard() {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+
+struct Profile {
+    bool enabled = false;
+    int stride = 1;        // time every stride-th pv_analysis / pv_resynthesis / pv_process call
+    long long calls = 0;
+    bool active = true;    // this call's launches are timed
+    // consecutive launches of one call share an event: launch i's stop is launch i+1's start
+    // (nothing else is enqueued between them), one event record per launch instead of two
+    bool chain_ok = false;
+    hipEvent_t chain_ev = nullptr;
+    hipStream_t chain_s = nullptr;
+    std::vector<hipEvent_t> ev_start, ev_stop;
+    std::vector<char> ev_shared;   // ev_start[i] is ev_stop[i-1] (returned to the pool once)
+    std::vector<hipEvent_t> pool;  // read-out events, reused (hipEventCreate per launch costs µs)
+    std::vector<int> ev_kernel;
+    double total_ms[kNumKernels] = {0};
+    int launches[kNumKernels] = {0};
+};
+
+}  // namespace pvhost
+
+struct pv_handle {
+    pv_config cfg{};
+    int N = 0, hop = 0, hs = 0, L_ana = 0, L_syn = 0, bins = 0, bins_pad = 0;
+    int spec_bins = 0, spec_stride = 0, F = 16, tail_len = 0, max_runs = 0;
+    int F_fused = 0;  // frames per run of the single-launch q = 1 path (0: not available)
+    pvtab::EnvOverrides env;  // environment overrides, read once by pv_create (pv.h lists them)
+    int src_hi = 0;   // highest analysis bin any output bin reads (pitch map; L otherwise)
+    int tables_ready = 1;  // 0: pv_config.tables_external until pv_import_tables
+    int mode = 0, effect = 0, pitch = 0, aligned_hop = 1, nan_faithful = 0;
+    int packed = 0;  // PV_SPEC_PACKED rows (STANDARD)
+    int phase_lock = 0;  // pv_set_phase_lock: identity phase locking (k_synthesis_locked)
+    // pv_set_formant: lifter order of the formant-preserving pitch shift (0: off), and the
+    // handle's envelope rows [max_channels][max_frames][env_stride] fp32 (allocated once, zeroed;
+    // a harmoniser's voices read voice 0's)
+    int formant = 0;
+    int env_stride = 0;
+    pvhost::DevBuf<float> d_env;
+    // pv_pitch_reserve: the resampler of pv_pitch_process (P = out hop, Q = hop) and the scratch
+    // rows the time stretch writes for it, [max_channels][ld_pitch] fp32
+    pv_resampler* pitch_rs = nullptr;
+    pvhost::DevBuf<float> d_pitch;
+    long long ld_pitch = 0;
+    float scale = 1.0f, rho = 1.0f, inv_q = 1.0f;
+    unsigned long long p_mod = 0, q = 1;
+    int q_pow2 = 1;
+    int k_lane = 0;  // e_k and (p j_k) mod q depend on k mod 64 only (synthesis LANEK kernels)
+    // device tables
+    pvhost::DevBuf<float> d_win, d_gain, d_ek;
+    pvhost::DevBuf<float2> d_tw_ana, d_tws_ana, d_tw_syn, d_tws_syn;
+    pvhost::DevBuf<unsigned> d_jk_mod;
+    pvhost::DevBuf<int> d_src_first, d_src_cnt;
+    // workspace
+    pvhost::DevBuf<int> d_runsum, d_carry;
+    pvhost::DevBuf<int> d_seg_carry;  // [C][bins_pad] unwrap count before a stream segment
+    pvhost::DevBuf<float> d_seg_phi;  // [C][bins_pad] phase of the frame before it
+    pvhost::DevBuf<float> d_tails;
+    // pv_process without a spectrum buffer on the split path: the handle's own rows
+    // (max_channels x max_frames, zeroed; allocated by pv_reserve_spectrum or the first such
+    // call outside a stream capture — spec_mu orders concurrent first calls)
+    pvhost::DevBuf<pv_float2> d_spec_own;
+    std::mutex spec_mu;
+    pvhost::DevBuf<int> d_seam_flags;  // fused path: per (channel, workgroup) arrival counters
+#ifdef PV_FUSED_STAMPS
+    pvhost::DevBuf<unsigned long long> d_stamps;  // diagnostic build: per-wave phase stamps of k_fused
+    size_t n_stamps = 0;
+#endif
+    pvhost::Profile prof;
+};
+
+// pv_rt: a pv_handle (tables) + per-channel stream state + an optional captured graph
+// of one callback (pinned host in -> device -> pv_rt_push -> pinned host out).
+struct pv_rt {
+    pv_handle* h = nullptr;
+    int channels = 0;
+    pvhost::DevBuf<float> d_hist, d_ola, d_phprev;
+    pvhost::DevBuf<int> d_M;
+    pvhost::DevBuf<unsigned> d_tcount;
+    int phase_lock = 0;  // pv_rt_set_phase_lock: k_rt in kModeLocked
+    // pv_rt_pitch_reserve: the streaming resampler of pv_rt_pitch_push (P = out hop, Q = hop,
+    // reduced).  d_prow: [channels][ld_prow] scratch rows [H history | max_nframes * out hop new
+    // stretched samples]; d_ptab: [Q][2W] coefficients (nullptr at ratio 1: no resampling)
+    int pitch_on = 0, pitch_P = 1, pitch_Q = 1, pitch_W = 0, pitch_H = 0, pitch_D = 0, pitch_max = 0;
+    pvhost::DevBuf<float> d_prow, d_ptab;
+    long long ld_prow = 0;
+    // captured callback
+    int g_nframes = 0;
+    pvhost::DevBuf<float, true> h_in, h_out;
+    pvhost::DevBuf<float> d_in, d_out;
+    hipStream_t g_stream = nullptr;
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    float *m_in = nullptr, *m_out = nullptr;  // device views of h_in / h_out (zero-copy)
+    int direct = 0;  // PV_RT_LAUNCH=direct: launch pv_rt_push per callback instead of replaying
+                     // the captured graph (BASELINE config 5's form, the default): measured p50
+                     // 21 vs 28 us per callback on ROCm 7.2
+};
+
+// pv_resampler: a reduced ratio P:Q, a quality preset and the polyphase coefficient table in
+// device memory (pv_resample.hpp)
+struct pv_resampler {
+    int P = 1, Q = 1, quality = 0, device = 0;
+    pv::ResamplePlan plan{};
+    pvhost::DevBuf<float4> d_tab;  // nullptr at ratio 1: the rows are copied
+};
+
+namespace pvhost {
+
+// ---- profiler (pv_api.cpp)
+// one public call (pv_analysis / pv_resynthesis / pv_process / pv_rt_push): with a stride k > 1 only every
+// k-th call's launches get events (each event record costs the queue a few us, which a
+// 40-us single-stream step would otherwise carry in its timed region)
+inline void prof_tick(pv_handle* h) {
+    if (h->prof.enabled) h->prof.active = (h->prof.calls++ % h->prof.stride) == 0;
+}
+// the event records around a timed launch; untimed launches pay two tests, inline
+pv_status prof_begin_timed(pv_handle* h, int kernel, hipStream_t s);
+pv_status prof_end_timed(pv_handle* h, hipStream_t s);
+inline bool prof_timed(const pv_handle* h) { return h->prof.enabled && h->prof.active; }
+inline pv_status prof_begin(pv_handle* h, int kernel, hipStream_t s) {
+    return prof_timed(h) ? prof_begin_timed(h, kernel, s) : PV_OK;
+}
+inline pv_status prof_end(pv_handle* h, hipStream_t s) { return prof_timed(h) ? prof_end_timed(h, s) : PV_OK; }
+
+// the launches of one pv_analysis / pv_resynthesis / pv_process call, which enqueue nothing
+// but kernels, may chain their events
+struct ProfCall {
+    pv_handle* h;
+    explicit ProfCall(pv_handle* hh) : h(hh) {
+        prof_tick(h);
+        h->prof.chain_ok = true;
+        h->prof.chain_ev = nullptr;
+    }
+    ~ProfCall() { h->prof.chain_ok = false; h->prof.chain_ev = nullptr; }
+};
+
+#define PV_LAUNCH(h, kid, s, call)                                                    \
+    do {                                                                              \
+        pv_status st_ = prof_begin(h, kid, s);                                        \
+        if (st_ != PV_OK) return st_;                                                 \
+        hipError_t e_ = (call);                                                       \
+        if (e_ != hipSuccess)                                                         \
+            return fail(PV_ERR_HIP, std::string(kKernelNames[kid]) + " launch: " +    \
+                                        hipGetErrorString(e_));                       \
+        st_ = prof_end(h, s);                                                         \
+        if (st_ != PV_OK) return st_;                                                 \
+    } while (0)
+
+// ---- checks several entry points share (pv_api.cpp)
+pv_status check_common(const pv_handle* h, int channels, int frames);
+// a caller's pv_config was built against this pv.h: checked before any other field is read
+pv_status check_abi(const pv_config* cfg);
+// "<fn>: quality must be 0 (fast) or 1 (best)"
+pv_status check_quality(const char* fn, int quality);
+// "<fn>: STANDARD time-stretch handles only"
+pv_status check_std_stretch(const char* fn, const pv_handle* h);
+
+inline int nruns_of(const pv_handle* h, int frames) { return (frames + h->F - 1) / h->F; }
+// the analysis keeps e_k in a register per lane (k_std_analysis EK_LANE)
+inline bool ek_lane_of(int hop_div, int bins) { return 64 % hop_div == 0 && bins >= 64; }
+// the single launch serves the handle's pv_process calls (phase locking and formant
+// preservation run on the split path)
+inline bool single_launch(const pv_handle* h) { return h->F_fused > 0 && !h->phase_lock && !h->formant; }
+
+// ---- launch sequences (pv_api_batch.cpp)
+// the state before a segment of a longer stream (pv_segment_resynthesis)
+struct SegState {
+    const int* carry_in;
+    const float* phi_in;
+    unsigned t_off;
+};
+pv_status do_analysis(pv_handle* h, const float* x, long long ldx, long long n, int C, int frames,
+                      pv_float2* spec, long long ld_spec, bool want_runsum, hipStream_t s, int src_hi = -1);
+pv_status do_envelope(pv_handle* h, const pv_float2* spec, long long ld_spec, int C, int frames, int order,
+                      float* env, long long ld_env, int env_stride, int env_tail, hipStream_t s);
+pv_status do_resynthesis(pv_handle* h, const pv_float2* spec, long long ld_spec, int C, int frames,
+                         const float* ola_in, long long ld_ola, float* out, long long ldo, bool have_runsum,
+                         hipStream_t s, const int* carry_from = nullptr, bool force_scan = false,
+                         const SegState* seg = nullptr, const float* env_from = nullptr);
+pv_status do_fused(pv_handle* h, const float* x, long long ldx, long long n, int C, int frames, pv_float2* spec,
+                   long long ld_spec, float* out, long long ldo, hipStream_t s);
+// pv_process after its checks (the caller holds the device guard and the profile call)
+pv_status process_impl(pv_handle* h, const float* x, long long ldx, long long n_samples, int channels, int frames,
+                       pv_float2* spec, long long ld_spec, float* out, long long ldo, hipStream_t s);
+// own_rows: allocate the handle's envelope rows (a harmoniser's voices k > 0 read voice 0's)
+pv_status set_formant(pv_handle* h, int order, bool own_rows);
+
+// ---- resampler (pv_api_resample.cpp)
+// the launch of pv_resample / pv_pitch_process (arguments checked by the caller)
+hipError_t resample_rows(const pv_resampler* rs, const float* x, long long ldx, long long n_in, int channels,
+                         float* y, long long ldy, hipStream_t s);
+
+}  // namespace pvhost
+#pragma GCC visibility pop

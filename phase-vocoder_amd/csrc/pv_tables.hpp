@@ -1,0 +1,89 @@
+// pv_tables.hpp — the arithmetic behind a handle: table recipes, the rational output-phase
+// factor, the pitch map, the run-length choices and the resampler's coefficients.
+// Plain C++17 on the host, no HIP header and no device call: every value the numerics contract
+// rests on can be computed, compared with the oracle and sanitised without a GPU
+// (host/tables_dump.cpp, tests/test_tables_host.py).  Each formula is the oracle's (pvref.c) in
+// its exact form and evaluation order; built with -ffp-contract=off like the rest.
+#pragma once
+#include <vector>
+
+#include "../../include/pv.h"
+
+#pragma GCC visibility push(hidden)
+namespace pvtab {
+
+constexpr double kPi = 3.14159265358979323846;
+// rounds of workgroups are counted on the MI355X's CUs whatever device a handle is on
+constexpr int kRoundCUs = 256;
+
+bool is_pow2(long long v);
+
+// ---- windows, synthesis gains (STANDARD; REF_COMPAT: win / N), twiddles
+void hann_periodic(int N, std::vector<float>& w);
+void hann_ref(int N, std::vector<float>& w);
+void hamming_ref(int N, std::vector<float>& w);
+void std_gain(int N, int hs, std::vector<float>& gain);
+void compat_gain(const std::vector<float>& win, std::vector<float>& gain);
+pv_float2 tw_entry(long long m, long long L);
+void stage_twiddles(int L, std::vector<pv_float2>& t);
+void fft_table(int L, std::vector<pv_float2>& t, bool v3 = false);
+int tw_syn_len(int L);
+void tw_syn_table(int L, std::vector<pv_float2>& t);  // the whole d_tw_syn block, tw_syn_len(L) entries
+void split_twiddles(int N, std::vector<pv_float2>& t);
+
+// ---- geometry of a configuration (phaseVocoder.h:79, :104)
+struct Geometry {
+    int hop, hs, pitch, L_ana, L_syn, bins, bins_pad, tail_len;
+};
+Geometry geometry(int N, int hop_div, int mode, int effect, float scale);
+
+// ---- unwrap tables and the rational output-phase factor rho = p/q
+struct PhaseTables {
+    std::vector<float> ek;
+    std::vector<long long> jk;
+    std::vector<unsigned> jk_mod;  // (p_mod * (j_k mod q)) mod q
+    float rho = 1.0f, inv_q = 1.0f;
+    unsigned long long p = 1, q = 1, p_mod = 0;
+    int q_pow2 = 1;
+};
+void phase_tables(int N, const Geometry& g, float scale, PhaseTables& t);
+// every bin k < L repeats bin k mod 64, and bin L's e equals bin 0's (feeds k_lane)
+bool bins_repeat_mod64(const PhaseTables& t);
+
+// ---- pitch map: k' = floor(beta*k + 0.5) (magnitudes summed, phase from smallest k)
+struct PitchMap {
+    std::vector<int> first, cnt;
+    int src_hi = 0;  // highest analysis bin any output bin reads (bins - 1 without a map)
+};
+void pitch_map(int bins, bool pitch, float scale, PitchMap& m);
+
+// ---- environment overrides (pv.h lists them), read once per pv_create
+struct EnvOverrides {
+    int compat_ana_frames = 4;                 // PV_COMPAT_ANA_FRAMES in [1, 256]
+    int fused_half = 1, fused_balance = 1;     // PV_FUSED_HALF=0, PV_FUSED_BALANCE=0
+    int run_frames = 0, fused_frames = 0;      // PV_RUN_FRAMES, PV_FUSED_FRAMES as given (0: unset)
+    int fused = 1, syn_lanek = 1;              // PV_FUSED=0, PV_SYN_LANEK=0
+};
+EnvOverrides read_env_overrides();
+
+// ---- run lengths
+// choose_run_frames fits F to whole rounds: the caller then asks the analysis kernel for its
+// workgroups per CU and waves per workgroup (pv::std_analysis_wgs_per_cu)
+bool run_fit_applies(long long work, int L_syn, int L_ana, int mode);
+// frames per wave-run F; wgs_per_cu <= 0: no round fit.  C, T: max_channels, max_frames (>= 1)
+int choose_run_frames(long long work, int L_syn, int L_ana, int mode, int wgs_per_cu, int waves_per_wg,
+                      long long C, long long T, int hs, int tail_len, const EnvOverrides& env);
+// frames per run of the single launch (q = 1), 0 with PV_FUSED=0
+int choose_fused_frames(int F, long long work, int hs, int tail_len, const EnvOverrides& env);
+// workgroups of the single launch and, when its rounds are balanced, the runs one frame longer
+void fused_rounds(int frames, int F, bool balance, int* nwg, int* n4);
+
+// ---- resampler presets (include/pv.h)
+double bessel_i0(double x);
+long long gcd_ll(long long a, long long b);
+int resample_half_width(int P, int Q, int quality);
+void resample_row(int P, int Q, int quality, int W, int r, float* row);
+long long resample_length(int P, int Q, long long n_in);
+
+}  // namespace pvtab
+#pragma GCC visibility pop

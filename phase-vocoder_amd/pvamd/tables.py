@@ -1,4 +1,5 @@
-"""Host copies of the handle's window tables (same double->float recipes as pv_api.cpp)."""
+"""Host copies of the handle's window tables (same double->float recipes as csrc/pv_tables.cpp;
+tests/test_tables_host.py compares the two and the oracle bit for bit)."""
 from __future__ import annotations
 
 import numpy as np

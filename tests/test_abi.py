@@ -215,7 +215,7 @@ def test_device_asm_has_no_prefetch_or_scc_hazards(device_asm):
 
 def test_rt_and_harmonizer_create_reject_bad_configs_without_touching_gpu():
     """pv_rt_create / pv_harmonizer_create check the ABI version before any other field
-    (ADVICE r5), then their own limits, all before a device call (pv_api.cpp)."""
+    (ADVICE r5), then their own limits, all before a device call (pv_api_rt.cpp, pv_api_misc.cpp)."""
     L = _lib.lib()
     h = ctypes.c_void_p()
     ratios = (ctypes.c_float * 2)(1.5, 0.5)
