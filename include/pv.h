@@ -79,7 +79,7 @@ extern "C" {
                                 pv_resample_length, pv_pitch_reserve / pv_pitch_process /
                                 pv_pitch_output_length, pv_rt_set_phase_lock /
                                 pv_rt_get_phase_lock, pv_rt_pitch_reserve / pv_rt_pitch_latency /
-                                pv_rt_pitch_push) */
+                                pv_rt_pitch_push, pv_pitch_set_formant / pv_pitch_get_formant) */
 
 typedef struct pv_handle pv_handle;
 
@@ -258,7 +258,8 @@ pv_status pv_segment_resynthesis(pv_handle* h, const pv_float2* spec, long long 
  * output is the same bits as with a spectrum buffer. */
 /* allocate (once, zeroed) the handle's own spectrum rows that pv_process(spec = NULL) uses
  * on the split path, so that such calls can then be captured into a graph; thread-safe; a
- * no-op for a single-launch handle (unless phase locking or formant preservation is on).  Not
+ * no-op for a single-launch handle (unless phase locking, formant preservation or
+ * pv_pitch_set_formant is on).  Not
  * capturable itself (it allocates). */
 pv_status pv_reserve_spectrum(pv_handle* h);
 
@@ -369,6 +370,39 @@ long long pv_pitch_output_length(const pv_handle* h, int frames);
 pv_status pv_pitch_process(pv_handle* h, const float* x, long long ldx, long long n_samples,
                            int channels, int frames, pv_float2* spec, long long ld_spec, float* out,
                            long long ldo, void* stream);
+
+/* Formant preservation for the pitch shift by time stretch and resampling.
+ * The stretch keeps the spectral envelope in place and the resampling by out_hop / hop then
+ * moves it with the partials.  With order > 0 every frame of the stretch is pre-warped so that
+ * the resampling puts the envelope back where the input had it.  Per frame, with L = N/2 and
+ * le[k] the log envelope of pv_set_formant (same order, same floor, same kernel):
+ *   a = k out_hop, i_k = a div hop, r_k = a mod hop (exact integers); from the first bin with
+ *   i_k >= L on, i_k = L and r_k = 0 (those bins land above the output's Nyquist frequency and
+ *   the resampler's low-pass removes them);
+ *   lw[k] = le[i_k] + (r_k / hop) (le[min(i_k + 1, L)] - le[i_k]);
+ *   |Y[k]| = mag[k] exp(lw[k] - le[k]);
+ * the output phase is the stretch's, unlocked or locked (pv_set_phase_lock: both settings
+ * compose with this one); peaks and owners are decided on the frame's own magnitudes, the warp is
+ * a positive real gain applied after every decision.  No state between frames: the analysis, the
+ * spectrum rows, the unwrap decisions and the stream segments are unchanged.  At out_hop = hop the
+ * gain is exp(0) = 1 and the output is the plain one.
+ * order = 0 (default): off.  order in [1, N/4]: on.  Other values: PV_ERR_ARG.  STANDARD +
+ * PV_TIME_SHIFT handles; REF_COMPAT or PV_PITCH_SHIFT: PV_ERR_UNSUPPORTED (pv_set_formant keeps
+ * its meaning and its refusals).  NULL handle: PV_ERR_ARG (0 from the get call).  A setup call
+ * (not capturable), ordered like the handle's compute calls.  The first call with order > 0
+ * allocates, zeroed, the envelope rows of pv_set_formant (max_channels x max_frames rows of
+ * N/2 + 16 floats; PV_ERR_NOMEM: the feature stays off) and uploads the warp map {i_k, r_k / hop}
+ * (built on the host; not part of the exported tables: a tables_external handle builds its own).
+ * While it is on, pv_resynthesis, pv_process and pv_segment_resynthesis run the envelope kernel
+ * and then the warp synthesis kernel, so pv_pitch_process stays "pv_process into the scratch rows,
+ * then pv_resample"; a single-launch handle takes the split path (pv_info.single_launch reads 0,
+ * pv_process(spec = NULL) uses the handle's own rows: pv_reserve_spectrum) and goes back to the
+ * single launch with order 0.
+ * The feature is for harmonic-rich signals.  A lone sinusoid has no formants: its envelope is
+ * the partial itself, and the warp attenuates it (DESIGN.md §3.10 has figures).
+ * pv_rt and the harmoniser have no such switch. */
+pv_status pv_pitch_set_formant(pv_handle* h, int order);
+int pv_pitch_get_formant(const pv_handle* h);
 
 /* ---------------------------------------------------------------- real-time mode
  * A pv_rt streams `channels` mono channels through the STANDARD pipeline one callback at a

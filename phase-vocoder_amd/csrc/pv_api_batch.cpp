@@ -3,6 +3,7 @@
 // formant preservation, the handle's own spectrum rows).
 #include <algorithm>
 #include <cstdint>
+#include <cstring>
 
 #include "pv_host.hpp"
 
@@ -191,6 +192,19 @@ pv_status do_resynthesis(pv_handle* h, const pv_float2* spec, long long ld_spec,
         p.ld_env = ld_env;
         p.env_stride = h->env_stride;
         PV_LAUNCH(h, KSF, s, pv::launch_synthesis_formant(h->L_syn, C, p, s));
+    } else if (h->pitch_formant) {  // (STANDARD + PV_TIME_SHIFT: pv_pitch_set_formant, locked or not)
+        if (!h->d_env || !h->d_warp_idx || !h->d_warp_frac)
+            return fail(PV_ERR_ARG, "the envelope warp is on but the handle has no envelope rows or warp map");
+        const long long ld_env = (long long)h->cfg.max_frames * h->env_stride;
+        pv_status se = do_envelope(h, spec, ld_spec, C, frames, h->pitch_formant, h->d_env, ld_env, h->env_stride,
+                                   16, s);
+        if (se != PV_OK) return se;
+        p.env = h->d_env;
+        p.ld_env = ld_env;
+        p.env_stride = h->env_stride;
+        p.src_first = h->d_warp_idx;  // (a time stretch has no pitch map: the fields carry the warp map)
+        p.src_cnt = h->d_warp_frac;
+        PV_LAUNCH(h, KSW, s, pv::launch_synthesis_warp(h->L_syn, h->phase_lock, C, p, s));
     } else if (h->phase_lock)  // (STANDARD + PV_TIME_SHIFT: pv_set_phase_lock)
         PV_LAUNCH(h, KSL, s, pv::launch_synthesis_locked(h->L_syn, C, p, s));
     else
@@ -286,25 +300,36 @@ pv_status reserve_spec_own(pv_handle* h) {
 }
 }  // namespace
 
+namespace {
+// the handle's envelope rows (pv_set_formant, pv_pitch_set_formant): allocated once, zeroed
+pv_status reserve_env_rows(pv_handle* h, const char* fn) {
+    h->env_stride = h->L_syn + 16;
+    if (h->d_env) return PV_OK;
+    DeviceGuard g(h->cfg.device);
+    // rows of N/2 + 16 floats: bin N/2 and 15 zeros make every row store whole 64-byte segments
+    const int stride = h->L_syn + 16;
+    const size_t n = (size_t)std::max(h->cfg.max_channels, 1) * (size_t)std::max(h->cfg.max_frames, 1) *
+                     (size_t)stride;
+    DevBuf<float> rows;
+    if (rows.alloc(n) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(PV_ERR_NOMEM, std::string(fn) + ": envelope rows");
+    }
+    if (hipMemset(rows.p, 0, sizeof(float) * n) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+        return fail(PV_ERR_HIP, std::string(fn) + ": zeroing the envelope rows");
+    h->d_env = std::move(rows);
+    return PV_OK;
+}
+}  // namespace
+
 pv_status set_formant(pv_handle* h, int order, bool own_rows) {
     if (!h) return fail(PV_ERR_ARG, "null handle");
     if (h->mode != PV_MODE_STANDARD || h->effect != PV_PITCH_SHIFT)
         return fail(PV_ERR_UNSUPPORTED, "pv_set_formant: STANDARD pitch-shift handles only");
     if (order < 0 || order > h->N / 4) return fail(PV_ERR_ARG, "pv_set_formant: order must be in [0, N/4]");
-    if (order > 0 && own_rows && !h->d_env) {
-        DeviceGuard g(h->cfg.device);
-        // rows of N/2 + 16 floats: bin N/2 and 15 zeros make every row store whole 64-byte segments
-        const int stride = h->L_syn + 16;
-        const size_t n = (size_t)std::max(h->cfg.max_channels, 1) * (size_t)std::max(h->cfg.max_frames, 1) *
-                         (size_t)stride;
-        DevBuf<float> rows;
-        if (rows.alloc(n) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(PV_ERR_NOMEM, "pv_set_formant: envelope rows");
-        }
-        if (hipMemset(rows.p, 0, sizeof(float) * n) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
-            return fail(PV_ERR_HIP, "pv_set_formant: zeroing the envelope rows");
-        h->d_env = std::move(rows);
+    if (order > 0 && own_rows) {
+        pv_status st = reserve_env_rows(h, "pv_set_formant");
+        if (st != PV_OK) return st;
     }
     h->env_stride = h->L_syn + 16;
     h->formant = order;
@@ -455,6 +480,38 @@ int pv_get_phase_lock(const pv_handle* h) { return h ? h->phase_lock : 0; }
 pv_status pv_set_formant(pv_handle* h, int order) { return set_formant(h, order, true); }
 
 int pv_get_formant(const pv_handle* h) { return h ? h->formant : 0; }
+
+pv_status pv_pitch_set_formant(pv_handle* h, int order) {
+    if (!h) return fail(PV_ERR_ARG, "null handle");
+    pv_status st = check_std_stretch("pv_pitch_set_formant", h);
+    if (st != PV_OK) return st;
+    if (order < 0 || order > h->N / 4) return fail(PV_ERR_ARG, "pv_pitch_set_formant: order must be in [0, N/4]");
+    if (order > 0) {
+        // on a failure the feature stays as it was (off, on a first call)
+        if ((st = reserve_env_rows(h, "pv_pitch_set_formant")) != PV_OK) return st;
+        // (the map is the handle's own, hop and out hop only: not part of the table blob, so a
+        // tables_external handle builds it here like any other)
+        if (!h->d_warp_idx || !h->d_warp_frac) {
+            DeviceGuard g(h->cfg.device);
+            std::vector<int> idx, bits;
+            std::vector<float> frac;
+            warp_map(h->bins, h->hop, h->hs, idx, frac);
+            bits.resize(frac.size());
+            std::memcpy(bits.data(), frac.data(), sizeof(float) * frac.size());
+            DevBuf<int> di, df;
+            if (di.upload(idx.data(), idx.size()) != hipSuccess || df.upload(bits.data(), bits.size()) != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(PV_ERR_NOMEM, "pv_pitch_set_formant: warp map");
+            }
+            h->d_warp_idx = std::move(di);
+            h->d_warp_frac = std::move(df);
+        }
+    }
+    h->pitch_formant = order;
+    return PV_OK;
+}
+
+int pv_pitch_get_formant(const pv_handle* h) { return h ? h->pitch_formant : 0; }
 
 pv_status pv_spectral_envelope(pv_handle* h, const pv_float2* spec, long long ld_spec, int channels, int frames,
                                int order, float* env, long long ld_env, void* stream) {

@@ -6,6 +6,7 @@
 #include "pv_device.hpp"
 #include "pv_lock.hpp"
 #include "pv_formant.hpp"
+#include "pv_warp.hpp"
 
 
 namespace pv {
@@ -230,7 +231,9 @@ struct SynLds {
 // already holds), MODE 1 REF_COMPAT (kernel.cu:121-129 y-bug), MODE 5: sv is the output
 // spectrum Y itself (k_fused MODE 4), MODE 6 (kModeLocked): MODE 0 with identity phase
 // locking (pv_lock.hpp), MODE 7 (kModeFormant): MODE 2 with the formant gather of
-// pv_formant.hpp (env: the frame's log envelope row).  tq = (t + 1) mod q.
+// pv_formant.hpp (env: the frame's log envelope row), MODE 8 / 9 (kModeWarp / kModeLockedWarp):
+// MODE 0 / kModeLocked with the envelope warp of pv_warp.hpp on the magnitudes (env as in MODE 7;
+// tb.srcl: the warp map).  tq = (t + 1) mod q.
 // Result: STORE_LAST: time samples in tile (natural order, padded); else the inverse
 // FFT's last-pass registers z (point lane + 64 last_slot(idx)).
 // QPOW2: the output-phase denominator q is a power of two <= 2^24 (compile-time path);
@@ -306,8 +309,10 @@ __device__ __forceinline__ void synth_frame(const float2 (&sv)[Geo<L>::E + 1], b
         }
         // locked (kModeLocked): phc is theta = phi_s - phi in revolutions, the same propagation
         // with rho / 2 pi - 1 / 2 pi in place of rho / 2 pi (lock_offsets, pv_lock.hpp)
-        static_assert(!(MODE == kModeLocked && Q1), "the locked synthesis has no Q1 form");
-        const float rrev = (MODE == kModeLocked) ? pm.rho_rev - kInv2Pi : pm.rho_rev;
+        constexpr bool LOCKED = mode_is_locked(MODE);
+        static_assert(!(LOCKED && Q1), "the locked synthesis has no Q1 form");
+        static_assert(!mode_is_warp(MODE) || (Env::ON && !Q1), "the envelope warp needs the envelope row");
+        const float rrev = LOCKED ? pm.rho_rev - kInv2Pi : pm.rho_rev;
         if constexpr (Q1) {
             PV_FOR_BINS(E, lane, { phc[i] = __builtin_fmaf(pm.rho_rev, ph[i], 0.0f); })
         } else if constexpr (RACC) {
@@ -505,11 +510,19 @@ __device__ __forceinline__ void synth_frame(const float2 (&sv)[Geo<L>::E + 1], b
                 if (k == 0 || k == L) y.y = 0.0f;  // C2R ignores Im of DC and Nyquist
                 Yr[i] = y;
             })
-        } else if constexpr (MODE == kModeLocked) {
+        } else if constexpr (LOCKED) {
             // every bin takes the phase offset of the peak that owns it and keeps its own
             // analysis phase: phi[k] + theta[own(k)] (a peak: its unlocked phase, up to rounding)
             float tho[E + 1];
             lock_offsets<L>(mag, phc, lane, reinterpret_cast<float*>(tile), tho);
+            if constexpr (mode_is_warp(MODE)) {
+                // the warp gain, after every peak and owner decision; its round trip through the
+                // tile stays after the theta reads
+                wave_lds_sync();
+                float wg[E + 1];
+                warp_gains<L>(env.v, srcl, reinterpret_cast<float*>(tile), lane, wg);
+                PV_FOR_BINS(E, lane, { mag[i] *= wg[i]; })
+            }
             PV_FOR_BINS(E, lane, {
                 float sn, cs;
                 sincos_rev(__builtin_fmaf(kInv2Pi, ph[i], tho[i]), &sn, &cs);
@@ -518,6 +531,11 @@ __device__ __forceinline__ void synth_frame(const float2 (&sv)[Geo<L>::E + 1], b
                 Yr[i] = y;
             })
         } else {
+            if constexpr (mode_is_warp(MODE)) {
+                float wg[E + 1];
+                warp_gains<L>(env.v, srcl, reinterpret_cast<float*>(tile), lane, wg);
+                PV_FOR_BINS(E, lane, { mag[i] *= wg[i]; })
+            }
             PV_FOR_BINS(E, lane, {
                 float sn, cs;
 #ifdef PV_ABL_NOSINCOS
@@ -554,7 +572,7 @@ __device__ __forceinline__ void synth_frame(const float2 (&sv)[Geo<L>::E + 1], b
         Bp[q].x = __int_as_float(__builtin_amdgcn_ds_bpermute(src_lane, __float_as_int(o.x)));
         Bp[q].y = __int_as_float(__builtin_amdgcn_ds_bpermute(src_lane, __float_as_int(o.y)));
     }
-    wave_lds_sync();  // the FFT's first tile store stays after the reads above (MODE 2, 3, locked)
+    wave_lds_sync();  // the FFT's first tile store stays after the reads above (MODE 2, 3, locked, warp)
 #pragma unroll
     for (int q = 0; q < E; ++q) {
         const float2 A = Yr[q];

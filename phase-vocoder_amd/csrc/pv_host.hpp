@@ -30,10 +30,11 @@ pv_status fail(pv_status s, const std::string& msg);
     } while (0)
 
 // kernel ids of the per-launch profile and their names (pv_profile_read), index for index
-enum { KA, KRS, KC, KS, KSEAM, KCA, KRT, KF, KSL, KENV, KSF, KRES, KRTR, kNumKernels };
+enum { KA, KRS, KC, KS, KSEAM, KCA, KRT, KF, KSL, KENV, KSF, KRES, KRTR, KSW, kNumKernels };
 inline constexpr const char* kKernelNames[] = {"analysis", "runsum", "carry", "synthesis", "seam",
                                                "compat_analysis", "rt", "fused", "synthesis_locked",
-                                               "envelope", "synthesis_formant", "resample", "rt_resample"};
+                                               "envelope", "synthesis_formant", "resample", "rt_resample",
+                                               "synthesis_warp"};
 static_assert(sizeof(kKernelNames) / sizeof(kKernelNames[0]) == kNumKernels, "one name per kernel id");
 
 // Move-only owner of one hipMalloc (Pinned: hipHostMalloc, device-mapped) allocation.  Converts
@@ -124,6 +125,10 @@ struct pv_handle {
     int formant = 0;
     int env_stride = 0;
     pvhost::DevBuf<float> d_env;
+    // pv_pitch_set_formant: lifter order of the envelope warp of the time stretch (0: off; the
+    // rows are d_env), and the warp map {i_k}, {bits of f_k} for k <= N/2 (pvtab::warp_map)
+    int pitch_formant = 0;
+    pvhost::DevBuf<int> d_warp_idx, d_warp_frac;
     // pv_pitch_reserve: the resampler of pv_pitch_process (P = out hop, Q = hop) and the scratch
     // rows the time stretch writes for it, [max_channels][ld_pitch] fp32
     pv_resampler* pitch_rs = nullptr;
@@ -246,9 +251,11 @@ pv_status check_std_stretch(const char* fn, const pv_handle* h);
 inline int nruns_of(const pv_handle* h, int frames) { return (frames + h->F - 1) / h->F; }
 // the analysis keeps e_k in a register per lane (k_std_analysis EK_LANE)
 inline bool ek_lane_of(int hop_div, int bins) { return 64 % hop_div == 0 && bins >= 64; }
-// the single launch serves the handle's pv_process calls (phase locking and formant
-// preservation run on the split path)
-inline bool single_launch(const pv_handle* h) { return h->F_fused > 0 && !h->phase_lock && !h->formant; }
+// the single launch serves the handle's pv_process calls (phase locking, formant preservation
+// and the envelope warp run on the split path)
+inline bool single_launch(const pv_handle* h) {
+    return h->F_fused > 0 && !h->phase_lock && !h->formant && !h->pitch_formant;
+}
 
 // ---- launch sequences (pv_api_batch.cpp)
 // the state before a segment of a longer stream (pv_segment_resynthesis)

@@ -251,6 +251,12 @@ hipError_t launch_synthesis_locked(int L, int channels, const SynParams& p, hipS
 // used), same tails for launch_seam.  L <= 1024.
 hipError_t launch_envelope(int L, int channels, const EnvParams& p, hipStream_t s);
 hipError_t launch_synthesis_formant(int L, int channels, const SynParams& p, hipStream_t s);
+// STANDARD time stretch with the envelope warp (pv_warp.hip; pv_pitch_set_formant): launch_synthesis's
+// mode 0, or launch_synthesis_locked with lock != 0, with every magnitude scaled by the frame's
+// envelope at the bin's warp position.  SynParams.env: the rows launch_envelope wrote;
+// src_first / src_cnt carry the warp map {i_k} / {bits of f_k}, k <= L (a time stretch has no
+// pitch map; k_lane and src_hi are not used); same tails for launch_seam.  L <= 1024.
+hipError_t launch_synthesis_warp(int L, int lock, int channels, const SynParams& p, hipStream_t s);
 // the synthesis kernel for this geometry can take SynParams.k_lane (register overlap-add,
 // power-of-two q, STANDARD)
 bool synthesis_lane_kernel(int L, int mode, int hs, bool q_pow2, unsigned long long q);

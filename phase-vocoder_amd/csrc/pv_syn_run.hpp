@@ -219,7 +219,7 @@ struct SynCarve {
     const float* gainl;  // N gains (unless GREG)
     const float* ekl;    // e_k
     const unsigned* jkl; // (p j_k) mod q, or its float / q (RACC)
-    const int* srcl;     // pitch map {first, count}
+    const int* srcl;     // pitch map {first, count}; warp modes: {i_k, bits of f_k} (pv_warp.hpp)
 };
 
 template <int L, int MODE, int DT, bool QPOW2>
@@ -313,7 +313,7 @@ __device__ __forceinline__ void syn_run(const SynParams& p, const SynCarve& sc, 
         for (int q = 0; q < E; ++q) twr.v[q] = lds_ld(&sc.twsl[lane + 64 * q]);
     }
     const unsigned q32 = (unsigned)p.q;  // <= 2^24 (QPOW2) or <= 32768
-    // (env: the frame's log envelope row, formant mode; NoEnv otherwise)
+    // (env: the frame's log envelope row, formant and warp modes; NoEnv otherwise)
     auto synth = [&](int u, int t, const float2 (&sv)[E + 1], float2 (&z)[E], const auto& hk, const auto& env) {
         // (t_off: a segment's first frame index in its whole stream, mod q)
         const unsigned tq = QPOW2 ? ((unsigned)(t + 1) + p.t_off) & (q32 - 1u) : ((unsigned)(t + 1) + p.t_off) % q32;
@@ -360,9 +360,9 @@ __device__ __forceinline__ void syn_run(const SynParams& p, const SynCarve& sc, 
         for (int s = 0; s < NS; ++s) acc[s] = (s + D < NS) ? acc[(s + D < NS) ? s + D : 0] : make_float2(0.0f, 0.0f);
     };
 
-    // formant mode: the frame's log envelope row (k_envelope wrote it), loaded one frame
-    // ahead like the spectrum row; every lane reads bin L's value (one address)
-    constexpr bool FORMANT = MODE == kModeFormant;
+    // formant and warp modes: the frame's log envelope row (k_envelope wrote it), loaded one
+    // frame ahead like the spectrum row; every lane reads bin L's value (one address)
+    constexpr bool FORMANT = MODE == kModeFormant || mode_is_warp(MODE);
     using EnvS = typename std::conditional<FORMANT, EnvReg<E>, NoEnv>::type;
     EnvS ev;
     auto load_env = [&](int t) {
@@ -377,7 +377,7 @@ __device__ __forceinline__ void syn_run(const SynParams& p, const SynCarve& sc, 
     // register copy sits between a row load and its vmcnt (scripts/prefetch_hazards.py,
     // tests/test_abi.py; at L <= 256 the compiler copies the row buffers)
     // (the formant synthesis reads its envelope rows with plain loads: no self-tracked prefetch)
-    constexpr bool FASTOK = ROLA && L == 512 && MODE != kModeFormant;
+    constexpr bool FASTOK = ROLA && L == 512 && !FORMANT;
     const bool fast = FASTOK && nfr == p.F && p.out_aligned && obase + (long long)p.F * hs <= p.out_len;
     if (FASTOK && fast) {
         // every store of the run is in bounds: trip u = [load row u+1] [frame u] [D stores]
@@ -416,7 +416,7 @@ __device__ __forceinline__ void syn_run(const SynParams& p, const SynCarve& sc, 
         // current row (synth_frame's hook, before the pre-step), into the same registers —
         // no copy of the row (34 VGPR moves per frame); the loads have the inverse FFT and
         // the overlap-add to land
-        constexpr bool LATE = ROLA && L >= 1024 && MODE != 2 && MODE != kModeFormant;  // (MODE 2: 260 VGPRs, 1 wave/SIMD)
+        constexpr bool LATE = ROLA && L >= 1024 && MODE != 2 && !FORMANT;  // (MODE 2: 260 VGPRs, 1 wave/SIMD)
         const bool fast_st = ROLA && p.out_aligned && obase + (long long)p.F * hs <= p.out_len;
         (void)fast_st;
         static_assert(NR == E || (MODE == 3 && NR < E), "partial rows: single-source pitch only");

@@ -196,6 +196,22 @@ void pitch_map(int bins, bool pitch, float scale, PitchMap& m) {
     }
 }
 
+// warp position of bin k after the P:Q resampling of the stretched signal, in exact integers:
+// a = k out_hop, i_k = a div hop, f_k = (a mod hop) / hop (the fp32 nearest: both are exact in
+// fp32 and the division is correctly rounded); from the first bin with i_k >= L on, {L, 0}
+void warp_map(int bins, int hop, int out_hop, std::vector<int>& idx, std::vector<float>& frac) {
+    const int L = bins - 1;
+    idx.assign(bins, L);
+    frac.assign(bins, 0.0f);
+    for (int k = 0; k < bins; ++k) {
+        const long long a = (long long)k * out_hop;
+        const long long i = a / hop, r = a % hop;
+        if (i >= L) continue;
+        idx[k] = (int)i;
+        frac[k] = (float)r / (float)hop;
+    }
+}
+
 EnvOverrides read_env_overrides() {
     EnvOverrides e;
     // the single-launch and REF_COMPAT overrides (pv.h)

@@ -57,6 +57,11 @@ struct PitchMap {
 };
 void pitch_map(int bins, bool pitch, float scale, PitchMap& m);
 
+// ---- envelope warp of the stretch-and-resample pitch shift (pv_pitch_set_formant; DESIGN.md
+// §3.10): bin k reads the frame's log envelope at k out_hop / hop = idx[k] + frac[k], clamped
+// to {L, 0}.  Not part of the exported table blob.
+void warp_map(int bins, int hop, int out_hop, std::vector<int>& idx, std::vector<float>& frac);
+
 // ---- environment overrides (pv.h lists them), read once per pv_create
 struct EnvOverrides {
     int compat_ana_frames = 4;                 // PV_COMPAT_ANA_FRAMES in [1, 256]

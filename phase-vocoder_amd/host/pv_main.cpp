@@ -17,6 +17,13 @@
 //                                        band-limited resampling (pv_pitch_process): --mode std
 //                                        with effect t, every channel in one call; composes with
 //                                        --phase-lock; not with --rt
+//     --pitch-formant ORDER              formant preservation for --pitch-resample
+//                                        (pv_pitch_set_formant, lifter order 1 .. N/4): the
+//                                        stretch is pre-warped so that the resampling leaves the
+//                                        spectral envelope where the input has it; needs
+//                                        --pitch-resample (--mode std, effect t); composes with
+//                                        --phase-lock; not with --rt.  For harmonic-rich signals:
+//                                        a lone sinusoid is its own envelope and is attenuated
 //     --single-arg                       PhaseVocoder(N): periodic Hann, hop N/2 (phaseVocoder.h:46-78)
 //     --nan-faithful                     atanf(0/0) = NaN phases as the reference (kernel.cu:101-109)
 //     --timer                            print CudaPhase::timer() per call (main.cpp:238-241, 275-278)
@@ -81,7 +88,7 @@ int main(int argc, char** argv) {
     int N = 256, hopdiv = 2;
     float scale = 1.0f;
     bool batched = false, single_arg = false, show_timer = false, rt = false, phase_lock = false;
-    int formant = 0;
+    int formant = 0, pitch_formant = 0;
     int pitch_resample = -1;  // --pitch-resample: quality preset (0 fast, 1 best)
     double ana_ms = 0.0, syn_ms = 0.0;
     pv_mode mode = PV_MODE_REF_COMPAT;
@@ -100,6 +107,7 @@ int main(int argc, char** argv) {
         else if (a == "--rt") rt = true;
         else if (a == "--phase-lock") phase_lock = true;
         else if (a == "--formant" && i + 1 < argc) formant = std::atoi(argv[++i]);
+        else if (a == "--pitch-formant" && i + 1 < argc) pitch_formant = std::atoi(argv[++i]);
         else if (a == "--pitch-resample" && i + 1 < argc) {
             const std::string q = argv[++i];
             if (q != "fast" && q != "best") {
@@ -166,6 +174,20 @@ int main(int argc, char** argv) {
         }
         if (pv_pitch_reserve(phase.handle, pitch_resample) != PV_OK) {
             std::fprintf(stderr, "err: --pitch-resample: %s\n", pv_last_error());
+            return 1;
+        }
+    }
+    if (pitch_formant != 0) {
+        if (rt) {
+            std::fprintf(stderr, "err: --pitch-formant: the real-time path has no formant preservation\n");
+            return 1;
+        }
+        if (pitch_resample < 0) {
+            std::fprintf(stderr, "err: --pitch-formant needs --pitch-resample fast|best\n");
+            return 1;
+        }
+        if (pv_pitch_set_formant(phase.handle, pitch_formant) != PV_OK) {
+            std::fprintf(stderr, "err: --pitch-formant: %s\n", pv_last_error());
             return 1;
         }
     }

@@ -11,6 +11,8 @@
 //         float  ek[B];  int64 jk[B];  uint32 jk_mod[B];  int32 src_first[B], src_cnt[B]
 //   tables_dump resample P Q quality [file]
 //       int64 head[4]  reduced P, reduced Q, quality, W;  then float row[Q][2W]
+//   tables_dump warp N hop out_hop [file]
+//       the envelope warp map (pv_pitch_set_formant): int32 idx[N/2 + 1], then float frac[N/2 + 1]
 //   tables_dump choose C T N hop_div mode effect scale wgs_per_cu waves_per_wg
 //       prints "F Ff": frames per run, and per run of the single launch (environment
 //       overrides apply, as in pv_create)
@@ -59,6 +61,7 @@ int usage() {
     std::fprintf(stderr,
                  "usage: tables_dump N hop_div mode effect scale window [file]\n"
                  "       tables_dump resample P Q quality [file]\n"
+                 "       tables_dump warp N hop out_hop [file]\n"
                  "       tables_dump choose C T N hop_div mode effect scale wgs_per_cu waves_per_wg\n"
                  "       tables_dump balance frames F\n");
     return 2;
@@ -139,6 +142,20 @@ int dump_resample(int argc, char** argv) {
     return 0;
 }
 
+int dump_warp(int argc, char** argv) {
+    if (argc < 5) return usage();
+    const int N = std::atoi(argv[2]), hop = std::atoi(argv[3]), hs = std::atoi(argv[4]);
+    if (!is_pow2(N) || N < 256 || N > 2048 || hop <= 0 || hop > N || hs <= 0 || hs > N) return usage();
+    std::vector<int> idx;
+    std::vector<float> frac;
+    warp_map(N / 2 + 1, hop, hs, idx, frac);
+    FILE* f = open_out(argc, argv, 5);
+    put(f, idx);
+    put(f, frac);
+    if (f != stdout) std::fclose(f);
+    return 0;
+}
+
 int choose(int argc, char** argv) {
     if (argc < 11) return usage();
     const long long C = std::atoll(argv[2]), T = std::atoll(argv[3]);
@@ -172,6 +189,7 @@ int main(int argc, char** argv) {
     if (argc < 2) return usage();
     const std::string cmd = argv[1];
     if (cmd == "resample") return dump_resample(argc, argv);
+    if (cmd == "warp") return dump_warp(argc, argv);
     if (cmd == "choose") return choose(argc, argv);
     if (cmd == "balance") return balance(argc, argv);
     return dump_tables(argc, argv);

