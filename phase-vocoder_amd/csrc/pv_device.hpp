@@ -620,7 +620,7 @@ __device__ __forceinline__ void load_tw0(float2 (&tw0)[Geo<L>::E], const float2*
 // its last pass would need an S (R - 1) ~ L-entry table, which costs the analysis a workgroup
 // per CU of LDS.
 // X: also at L = 1024 (radices 16, 16, 4; the batched synthesis's inverse transform, which no
-// contract binds — its table is pv_api.cpp's second d_tw_syn block)
+// contract binds — its table is the second block of d_tw_syn, tw_syn_table in pv_tables.cpp)
 template <int L, bool X = false>
 constexpr bool fft_v3() { return (L >= 128 && L <= 512) || (X && L == 1024); }
 // pass table offset of pass P >= 1: sum over 1 <= P' < P of S_P' (R_P' - 1)

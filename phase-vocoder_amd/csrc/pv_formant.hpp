@@ -3,7 +3,8 @@
 // low-quefrency part of its log magnitude, k_envelope in pv_formant.hip) whitens the source
 // bins before the gather and re-colours the gathered sum at the target bin:
 //   |Y[k']| = exp(le[k']) * sum over the sources k of k' of mag[k] exp(-le[k]).
-// Used by synth_frame's formant mode (pv_frame.hpp) in k_synthesis_formant.
+// Used by synth_frame's formant mode (pv_frame.hpp) in k_synthesis in the formant mode
+// (pv_syn_kernel.hpp, instantiated in pv_formant.hip).
 #pragma once
 #include "pv_device.hpp"
 

@@ -118,7 +118,7 @@ struct pv_handle {
     int tables_ready = 1;  // 0: pv_config.tables_external until pv_import_tables
     int mode = 0, effect = 0, pitch = 0, aligned_hop = 1, nan_faithful = 0;
     int packed = 0;  // PV_SPEC_PACKED rows (STANDARD)
-    int phase_lock = 0;  // pv_set_phase_lock: identity phase locking (k_synthesis_locked)
+    int phase_lock = 0;  // pv_set_phase_lock: identity phase locking (k_synthesis in the locked mode)
     // pv_set_formant: lifter order of the formant-preserving pitch shift (0: off), and the
     // handle's envelope rows [max_channels][max_frames][env_stride] fp32 (allocated once, zeroed;
     // a harmoniser's voices read voice 0's)

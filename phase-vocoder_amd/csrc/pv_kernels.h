@@ -104,7 +104,7 @@ struct SynParams {
                                        // source pitch: the row slots above it are not read)
     unsigned t_off;                    // (index of the first frame in the whole stream) mod q:
                                        // 0 unless a segment of a longer stream
-    // formant-preserving pitch shift (k_synthesis_formant; nullptr otherwise): the frames' log
+    // k_synthesis in the formant and warp modes (nullptr otherwise): the frames' log
     // envelope rows, env[c * ld_env + t * env_stride + k], k <= L (k_envelope)
     const float* env;
     long long ld_env;

@@ -6,13 +6,14 @@
 //   K2  k_carry (+ k_runsum when the spectrum did not come from K1)
 //         exclusive integer scan of the decisions over runs -> unwrap count at run start
 //   K3  k_synthesis<MODE>   phase propagation -> polar->rect -> inverse real FFT ->
-//         window -> overlap-add of the run in an LDS ring -> plain stores
+//         window -> overlap-add of the run in an LDS ring -> plain stores — pv_syn_kernel.hpp;
+//         here the launches of MODE 0..3
 //   K4  k_seam   adds each workgroup's overlap tail into the next workgroup's head
 //
 // Geometry: one frame per wavefront, and each wave owns a RUN of F consecutive frames of
 // one channel which it walks in order (the unwrap state stays in registers, the
 // overlap-add in a per-wave LDS ring).  A workgroup = 4 waves = 4 consecutive runs.
-#include "pv_syn_run.hpp"
+#include "pv_syn_kernel.hpp"
 
 namespace pv {
 
@@ -183,180 +184,6 @@ __global__ __launch_bounds__(256) void k_segcarry(SegParams p) {
     p.phi_in[(long long)c * BP + k] = prev;
 }
 
-// ------------------------------------------------------------------ K3 synthesis
-// One wave = one run of F frames (virtually padded to F: frames >= `frames` are zero).
-// MODE 0/2: STANDARD time stretch / pitch shift — output phase
-//         rho*(phi + 2 pi (M_dec + (t+1) j_k)), Hann synthesis window with
-//         the overlap normalisation folded into gain[].
-// MODE 1: REF_COMPAT — kernel.cu:352-432: x' = m cos(phi), y' = x' sin(phi), C2R N, /N,
-//         swap halves (rot = N/2), Hamming window (gain = w/N).
-// Overlap-add: a position is final once the frame that starts after it has been added;
-// final samples are stored straight to `out`.
-//   DT > 0 (out hop = 128 DT, L <= 1024): in registers.  After the inverse FFT's last pass
-//     lane holds points lane + 64 c, i.e. samples 2 lane + {0,1} + 128 c, so every
-//     position a lane ever touches is congruent to 2 lane (+1) mod 128: acc[c] covers run
-//     positions u*hs + 128 c + 2 lane + {0,1}; per frame the oldest DT slots are stored
-//     and the rest shift down.  No LDS ring, no final FFT store.  Runs away from the ends
-//     of the output take a loop with unconditional stores and a self-tracked prefetch
-//     of the next spectrum row (gload_pairs / vm_wait, pv_device.hpp).
-//   DT = 0 (any out hop): per-wave LDS ring of N samples.
-// After the loop the three intra-workgroup seams are closed from the neighbours' tails in
-// LDS (one barrier); the workgroup's last tail goes to `tails` for k_seam.
-// waves per SIMD the synthesis is compiled for (__launch_bounds__): L = 512 at <= 168
-// VGPRs; L = 1024 bounded at 1 only so that the compiler may use up to 256 VGPRs: the
-// kernels compile to <= 256 without AGPRs, so the 2 waves/SIMD their LDS sets hold
-// (tests/test_abi.py checks both)
-constexpr int kSynWaves512 = 3;
-constexpr int kSynWaves1024 = 1;
-template <int L, int MODE, int DT, bool QPOW2 = false, bool LANEK = false, int NR = Geo<L>::E>
-__global__ __launch_bounds__(256, (L <= 256) ? 4 : (L == 512) ? kSynWaves512 : (L == 1024) ? kSynWaves1024 : 1) void k_synthesis(SynParams p) {
-    using G_ = Geo<L>;
-    constexpr bool ROLA = DT > 0;
-    constexpr int E = G_::E;
-    constexpr int N = 2 * L;
-    constexpr int SPW = N / 64;  // samples per lane per frame
-    constexpr int B = L + 1;
-    constexpr bool GREG = SynTraits<L, MODE, DT, QPOW2>::GREG;  // ROLA gains in registers (else LDS)
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    float2* twl = reinterpret_cast<float2*>(smem);                     // L
-    float2* twsl = twl + L;                                            // L (+2 pad)
-    float2* tiles = twsl + (L + 2);                                    // 4 x TILE
-    float* after_tiles = reinterpret_cast<float*>(tiles + 4 * G_::TILE);
-    // 4 x N tails: ROLA writes them only after the frame loop, into the tile area
-    // (4 TILE float2 >= 4 N floats); the LDS ring of DT = 0 is live throughout
-    float* rings = ROLA ? reinterpret_cast<float*>(tiles) : after_tiles;
-    float* gainl = ROLA ? after_tiles : rings + 4 * N;                 // N (unless GREG)
-    float* ekl = gainl + (GREG ? 0 : N);                               // B (+pad)
-    unsigned* jkl = reinterpret_cast<unsigned*>(ekl + (B + 3));        // B (+pad)
-    int* srcl = reinterpret_cast<int*>(jkl + (B + 3));                 // 2 x B (pitch)
-    const int hs = p.hs;
-    const int TL = N - hs;
-    constexpr bool RACC = SynTraits<L, MODE, DT, QPOW2>::RACC;
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform: SGPR arithmetic
-    float2 tw0[Geo<L>::E];
-    load_tw0<L>(tw0, p.tw);
-    for (int i = tid; i < L; i += 256) { twl[i] = p.tw[i]; twsl[i] = p.tws[i]; }
-    if (!GREG)
-        for (int i = tid; i < N; i += 256) gainl[i] = p.gain[i];
-    if (MODE != 1) {
-        for (int i = tid; i < B; i += 256) {
-            ekl[i] = p.ek[i];
-            // RACC: (p j_k mod q) / q as a float (exact: q <= 4096)
-            jkl[i] = RACC ? __float_as_uint((float)p.jk_mod[i] * p.inv_q) : p.jk_mod[i];
-            if (MODE == 2) { srcl[2 * i] = p.src_first[i]; srcl[2 * i + 1] = p.src_cnt[i]; }
-            // MODE 3: the source's byte offset in a wave's tile, L + 1 (zero slot) if none
-            if (MODE == 3) srcl[i] = (int)sizeof(float2) * (p.src_first[i] >= 0 ? p.src_first[i] : L + 1);
-        }
-    }
-    float* ring = rings + w * N;  // ROLA: the run's tail, written after the frame loop
-    if (!ROLA) {
-#pragma unroll
-        for (int i = 0; i < SPW; ++i) ring[lane + 64 * i] = 0.0f;
-    }
-    __syncthreads();
-
-    const int c = blockIdx.y;
-    const int run = blockIdx.x * 4 + w;
-    const int t0 = run * p.F;
-    const int nfr = max(0, min(p.F, p.frames - t0));  // real frames of this wave's run
-    float* outc = p.out + (long long)c * p.ldo;
-    const long long obase = (long long)t0 * hs;
-
-    int M[E + 1];
-    float phprev[E + 1];
-    if (MODE != 1 && nfr > 0) {
-        // no carries when the output phase does not depend on the unwrap count (q = 1)
-        const int* cr = p.carry ? p.carry + ((long long)c * p.nruns + run) * p.bins_pad : nullptr;
-        if constexpr (RACC) {
-            const unsigned qm = (unsigned)p.q - 1u;
-            PV_FOR_BINS(E, lane, {
-                const unsigned mq = cr ? ((unsigned)p.p_mod * ((unsigned)cr[k] & qm)) & qm : 0u;
-                M[i] = __float_as_int((float)mq * p.inv_q);
-                phprev[i] = 0.0f;
-            })
-        } else {
-            PV_FOR_BINS(E, lane, { M[i] = cr ? cr[k] : 0; phprev[i] = 0.0f; })
-        }
-    }
-    constexpr int NS = SynTraits<L, MODE, DT, QPOW2>::NS, D = SynTraits<L, MODE, DT, QPOW2>::D;
-    float2 acc[NS];
-    syn_run<L, MODE, DT, QPOW2, LANEK, NR>(
-        p, SynCarve{twl, twsl, tiles, rings, gainl, ekl, jkl, srcl}, tw0, lane, w, c, t0, nfr, M, phprev, acc);
-    if constexpr (ROLA) {
-        // the run's tail (positions F*hs + j, j < N - hs) -> ring[j], over the tiles
-        __syncthreads();
-        float2* r2 = reinterpret_cast<float2*>(ring);
-#pragma unroll
-        for (int s = 0; s < NS - D; ++s) r2[64 * s + lane] = acc[s];
-    }
-    __syncthreads();
-    const int nwg = (p.nruns + 3) / 4;
-    const bool last = (blockIdx.x + 1 >= nwg);
-    if constexpr (ROLA && N > 128 * DT) {
-        if (p.out_aligned) {
-            // the overlap is TM = (N - 128 DT) / 128 float2 per lane at positions 2 lane +
-            // 128 m; positions are even and out_len is even, so a pair is wholly inside out
-            // or wholly past it.  The head read-back is one batch of loads and one wait (per
-            // 64 samples, a load-add-store was one serialized round trip: 14 at config 3)
-            constexpr int TM = (N - 128 * DT) / 128;
-            const float2* own2 = reinterpret_cast<const float2*>(ring) + lane;
-            if (w > 0) {
-                const float2* prev2 = reinterpret_cast<const float2*>(rings + (w - 1) * N) + lane;
-                f2v hd[TM];
-#pragma unroll
-                for (int m = 0; m < TM; ++m) {
-                    const long long gp = obase + 2 * lane + 128 * m;
-                    hd[m] = (gp < p.out_len) ? *reinterpret_cast<const f2v*>(outc + gp) : f2v{0.0f, 0.0f};
-                }
-#pragma unroll
-                for (int m = 0; m < TM; ++m) {
-                    const long long gp = obase + 2 * lane + 128 * m;
-                    const float2 t = prev2[64 * m];
-                    if (gp < p.out_len)
-                        __builtin_nontemporal_store(f2v{hd[m].x + t.x, hd[m].y + t.y}, reinterpret_cast<f2v*>(outc + gp));
-                }
-            }
-            if (w == 3) {
-                const long long nb = obase + (long long)p.F * hs + 2 * lane;
-                float* tdst = p.tails + ((long long)c * nwg + blockIdx.x) * p.tail_len + 2 * lane;
-#pragma unroll
-                for (int m = 0; m < TM; ++m) {
-                    const float2 v = own2[64 * m];
-                    if (last) {
-                        if (nb + 128 * m < p.out_len)
-                            __builtin_nontemporal_store(f2v{v.x, v.y}, reinterpret_cast<f2v*>(outc + nb + 128 * m));
-                    } else {
-                        *reinterpret_cast<f2v*>(tdst + 128 * m) = f2v{v.x, v.y};
-                    }
-                }
-            }
-            return;
-        }
-    }
-    // seams: run w's tail (positions F*hs + j) overlaps run w+1's head
-    if (w > 0) {
-        const float* prev = rings + (w - 1) * N;
-        for (int j = lane; j < TL; j += 64) {
-            const long long gp = obase + j;
-            if (gp < p.out_len) outc[gp] += prev[ROLA ? j : ((p.F * hs + j) & (N - 1))];
-        }
-    }
-    if (w == 3) {
-        float* tdst = p.tails + ((long long)c * nwg + blockIdx.x) * p.tail_len;
-        for (int j = lane; j < TL; j += 64) {
-            const float v = ring[ROLA ? j : ((p.F * hs + j) & (N - 1))];
-            if (last) {
-                const long long gp = obase + (long long)p.F * hs + j;
-                if (gp < p.out_len) outc[gp] = v;
-            } else {
-                tdst[j] = v;
-            }
-        }
-    }
-}
-
 // ------------------------------------------------------------------ K4 seam
 // adds each workgroup's last tail into the next workgroup's head (and ola_in at 0)
 __global__ __launch_bounds__(256) void k_seam(SeamParams p) {
@@ -430,7 +257,7 @@ hipError_t launch_window_gain(const float* win, float* dwin, float* gain, int n,
 }
 
 // ------------------------------------------------------------------ launchers
-// (syn_lds, syn_dt: pv_syn_run.hpp)
+// (syn_lds, syn_dt: pv_syn_kernel.hpp)
 size_t synthesis_lds_bytes(int L, int hs) {
     const int dt = syn_dt(L, hs);
     switch (L) {

@@ -1,7 +1,7 @@
 // pv_lock.hpp — identity phase locking of one STANDARD frame (Laroche & Dolson; DESIGN.md
 // §3.6): the peaks of the frame's magnitude row and, for every bin, the phase offset of the
-// peak that owns it.  Used by synth_frame's locked mode (pv_frame.hpp) in k_synthesis_locked
-// (pv_locked.hip).
+// peak that owns it.  Used by synth_frame's locked mode (pv_frame.hpp) in k_synthesis in
+// the locked mode (pv_syn_kernel.hpp, instantiated in pv_locked.hip).
 #pragma once
 #include "pv_device.hpp"
 

@@ -17,7 +17,7 @@
 // N - hop zeros, frame for frame (tests/test_gpu_rt.py).
 //
 // MODE kModeLocked (pv_rt_set_phase_lock): the stretch with identity phase locking, synth_frame's
-// locked step as in k_synthesis_locked (pv_locked.hip).  Its theta scratch is the wave's FFT
+// locked step as in k_synthesis in the locked mode (pv_locked.hip).  Its theta scratch is the wave's FFT
 // tile, which is free between the analysis split (read from registers) and the inverse FFT.
 // Locking adds no stream state.  Instantiations of their own: the k_rt<L, 0|2, ..> kernels keep
 // their code.

@@ -1,7 +1,7 @@
 // pv_syn_run.hpp — one wave's synthesis run (phase propagation -> polar->rect -> inverse
 // real FFT -> window -> overlap-add -> final samples to `out`) of the split path's K3
-// (k_synthesis, pv_kernels.hip), and the in-launch seam hand-off of the single-launch q = 1
-// path (pv_fused.hip).  Geometry and overlap-add: pv_kernels.hip, K3.
+// (k_synthesis, pv_syn_kernel.hpp), and the in-launch seam hand-off of the single-launch q = 1
+// path (pv_fused.hip).  Geometry and overlap-add: pv_syn_kernel.hpp, K3.
 #pragma once
 #include "pv_frame.hpp"
 #include "pv_kernels.h"
@@ -11,8 +11,7 @@ namespace pv {
 // Register-resident synthesis gains (the register overlap-add kernels, L <= 512, and L = 1024
 // with out hop 512: config 4, 252 VGPRs, free below the 2 waves/SIMD its LDS sets; smaller
 // out hops would need AGPRs).
-template <int L, int DT>
-constexpr bool syn_gains_in_regs() { return DT > 0 && (L <= 512 || (L == 1024 && DT == 4)); }
+constexpr bool syn_gains_in_regs(int L, int dt) { return dt > 0 && (L <= 512 || (L == 1024 && dt == 4)); }
 
 // sc1 (write-through) stores / loads of the inter-workgroup hand-offs (pv_fused.hip;
 // MI355X_MICROARCH.md "Valid forms")
@@ -228,7 +227,7 @@ struct SynTraits {
     static constexpr int E = Geo<L>::E;
     static constexpr int NS = ROLA ? E : 1;  // register overlap-add slots
     static constexpr int D = ROLA ? DT : 1;  // slots completed per frame (ROLA)
-    static constexpr bool GREG = syn_gains_in_regs<L, DT>();
+    static constexpr bool GREG = syn_gains_in_regs(L, DT);
     // revolution accumulator (synth_frame RACC; measured: synthesis -2.5 %); the host takes
     // the QPOW2 kernels only for q <= 4096
     static constexpr bool RACC = QPOW2 && MODE != 1;
@@ -495,22 +494,6 @@ __device__ __forceinline__ void syn_run(const SynParams& p, const SynCarve& sc, 
             }
         }
     }
-}
-
-// ------------------------------------------------------------------ launch geometry (host)
-template <int L>
-inline size_t syn_lds(int dt) {
-    const int ring_floats = (dt > 0) ? 0 : 4 * 2 * L;               // ROLA: tails alias the tiles
-    const int gain_floats = (dt > 0 && (L <= 512 || (L == 1024 && dt == 4))) ? 0 : 2 * L;  // syn_gains_in_regs
-    return sizeof(float2) * (L + (L + 2) + 4 * Geo<L>::TILE) +
-           sizeof(float) * (ring_floats + gain_floats) + sizeof(float) * 4 * (L + 1 + 3);
-}
-
-// register overlap-add slots per frame (out hop = 128 DT), 0 = LDS ring
-inline int syn_dt(int L, int hs) {
-    if (L > 1024 || hs % 128 != 0) return 0;
-    const int d = hs / 128;
-    return (d == 1 || d == 2 || d == 4) ? d : 0;
 }
 
 }  // namespace pv

@@ -5,7 +5,7 @@
 //   exp(lw[k] - le[k]),  lw[k] = le[i_k] + f_k (le[min(i_k + 1, L)] - le[i_k]),
 // so that after the P:Q resampling the envelope lies where the input had it.  The map
 // {i_k, f_k} is the host's (pvtab::warp_map).  Used by synth_frame's warp modes (pv_frame.hpp)
-// in k_synthesis_warp (pv_warp.hip).
+// in k_synthesis in the warp modes (pv_syn_kernel.hpp, instantiated in pv_warp.hip).
 #pragma once
 #include "pv_device.hpp"
 #include "pv_formant.hpp"

@@ -8,7 +8,8 @@ Variants, each with its own handle, in one process:
   parent   the locked stretch of another build of the library (--parent-lib, e.g.
            scripts/variant_from_rev.sh HEAD~ parent), when given
   off      the locked stretch of this build, the feature off
-  on       pv_pitch_set_formant(order): k_envelope + k_synthesis_warp in place of k_synthesis_locked
+  on       pv_pitch_set_formant(order): k_envelope + k_synthesis in the warp mode in place of
+           k_synthesis in the locked mode
 
 A round is `--warmup` untimed and `--steps` timed pv_process calls of one variant with the
 per-launch profile on (pv_profile_enable: device events around every launch); the variants take

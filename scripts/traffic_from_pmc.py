@@ -23,6 +23,18 @@ CALIB_BYTES = 8 * 512 * 131072
 NAMES = {"k_std_analysis": "analysis", "k_synthesis": "synthesis", "k_carry": "carry",
          "k_seam": "seam", "k_runsum": "runsum", "k_compat_analysis": "compat_analysis",
          "k_fft": "fft", "k_fused": "fused"}
+# k_synthesis<L, MODE, ..>: the locked / formant / warp modes are the same template
+# (pv_syn_kernel.hpp); "synthesis", which bench.py reads, stays the plain modes' (MODE 0..3)
+SYN_MODES = {6: "synthesis_locked", 7: "synthesis_formant", 8: "synthesis_warp", 9: "synthesis_locked_warp"}
+
+
+def key_of(kernel):
+    base, _, args = kernel.partition("<")
+    if base == "k_synthesis":
+        mode = int(args.split(",")[1])
+        return SYN_MODES.get(mode, "synthesis")
+    return NAMES.get(base, base)
+
 
 per = defaultdict(lambda: defaultdict(lambda: defaultdict(float)))  # kernel -> counter -> dispatch
 for f in sorted(glob.glob(os.path.join(root, "p*", "*counter_collection.csv"))):
@@ -47,8 +59,7 @@ res = {"_calibration": {"kernel": fft[0], "known_bytes": CALIB_BYTES,
                         "fetch_factor": fetch_f, "write_factor": write_f,
                         "source": root}}
 for k, cs in per.items():
-    base = k.split("<")[0]
-    name = NAMES.get(base, base)
+    name = key_of(k)
     rd = mean(cs["FETCH_SIZE"]) * 1024 * fetch_f
     wr = mean(cs["WRITE_SIZE"]) * 1024 * write_f
     res[name if name not in res else k] = {"kernel": k, "read_bytes_per_launch": rd,

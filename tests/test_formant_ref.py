@@ -94,7 +94,7 @@ def test_formant_symbols_and_null_handle():
 @pytest.mark.slow
 def test_formant_kernels_have_no_spills(tmp_path):
     """pv_formant.hip for gfx950 with the Makefile's device flags: k_envelope at the four sizes
-    and the 20 k_synthesis_formant instantiations spill no VGPR and use no scratch; the
+    and the 20 instantiations of k_synthesis in the formant mode spill no VGPR and use no scratch; the
     envelope kernel stays within the registers of its occupancy."""
     csrc = os.path.join(ROOT, "phase-vocoder_amd", "csrc")
     out = str(tmp_path / "pv_formant.s")
@@ -115,14 +115,19 @@ def test_formant_kernels_have_no_spills(tmp_path):
         elif cur and ":" in body:
             k, v = body.split(":", 1)
             rows[cur][k.strip()] = v.strip()
-    env = {}
+    env, syn = {}, 0
     for name, info in sorted(rows.items()):
         print(f"{name}: VGPRs {info['VGPRs']} spill {info['VGPRs Spill']} scratch {info['ScratchSize [bytes/lane]']}")
         assert info["VGPRs Spill"] == "0" and info["ScratchSize [bytes/lane]"] == "0", (name, info)
         m = re.match(r"_ZN2pv10k_envelopeILi(\d+)E", name)
         if m:
             env[int(m.group(1))] = int(info["VGPRs"])
-    assert len(rows) == 24 and sorted(env) == [128, 256, 512, 1024]
+            continue
+        # k_synthesis<L, MODE = kModeFormant (7), DT, QPOW2, LANEK = false, NR = L / 64>
+        m = re.match(r"_ZN2pv11k_synthesisILi(\d+)ELi7ELi(\d)ELb([01])ELb0ELi(\d+)EE", name)
+        assert m and int(m.group(4)) * 64 == int(m.group(1)), name
+        syn += 1
+    assert len(rows) == 24 and sorted(env) == [128, 256, 512, 1024] and syn == 20
     # 8 waves/SIMD up to L = 256 (<= 64 VGPRs), 6 at L = 512 (<= 80; 26 KB of LDS per workgroup:
     # 6 workgroups per CU), 3 at L = 1024 (<= 168; 51 KB: 3 workgroups per CU)
     assert env[128] <= 64 and env[256] <= 64 and env[512] <= 80 and env[1024] <= 168

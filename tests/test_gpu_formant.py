@@ -1,4 +1,4 @@
-"""Formant-preserving pitch shift on the GPU (pv_set_formant, k_envelope, k_synthesis_formant)
+"""Formant-preserving pitch shift on the GPU (pv_set_formant, k_envelope, k_synthesis in the formant mode)
 against the fp64 reference tests/formant_ref.py: the envelope kernel on its own, output parity
 over every size, overlap-add variant and ratio class of the split synthesis, spectrum / no
 spectrum / packed rows, the harmoniser, stream segments, a non-finite burst, graph capture,

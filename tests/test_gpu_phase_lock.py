@@ -1,4 +1,4 @@
-"""Identity phase locking on the GPU (pv_set_phase_lock, k_synthesis_locked) against the
+"""Identity phase locking on the GPU (pv_set_phase_lock, k_synthesis in the locked mode) against the
 fp64 reference tests/phase_lock_ref.py: every overlap-add variant and q path of the split
 synthesis, spectrum / no spectrum / packed rows / analysis + resynthesis, stream segments,
 the toggle and the refusals.  Runs of 8 frames (PV_RUN_FRAMES) and 76 frames per channel: 10

@@ -1,5 +1,5 @@
 """Formant preservation of the stretch-and-resample pitch shift on the GPU (pv_pitch_set_formant,
-k_envelope + k_synthesis_warp) against the fp64 reference tests/pitch_formant_ref.py: output
+k_envelope + k_synthesis in the warp mode) against the fp64 reference tests/pitch_formant_ref.py: output
 parity over every size, overlap-add variant and q path, unlocked and locked; natural and packed
 rows, resynthesis / process / process without a spectrum; pitch_process end to end; the
 identity at scale 1, the toggle, stream segments, graph capture, a non-finite burst, the

@@ -89,8 +89,8 @@ def test_phase_lock_symbols_and_null_handle():
 
 @pytest.mark.slow
 def test_locked_kernels_with_prefetch_have_no_spills(tmp_path):
-    """pv_locked.hip for gfx950 with the Makefile's device flags: the instantiations that
-    take syn_run's self-tracked row prefetch (register overlap-add at L = 512: DT 1, 2, 4)
+    """pv_locked.hip for gfx950 with the Makefile's device flags (k_synthesis in the locked
+    mode, and nothing else): the instantiations that take syn_run's self-tracked row prefetch (register overlap-add at L = 512: DT 1, 2, 4)
     must have no spilled VGPRs and no AGPRs (the prefetched registers may not be moved
     while the loads are in flight), and scripts/prefetch_hazards.py must pass on the assembly."""
     csrc = os.path.join(ROOT, "phase-vocoder_amd", "csrc")
@@ -114,8 +114,9 @@ def test_locked_kernels_with_prefetch_have_no_spills(tmp_path):
             rows[cur][k.strip()] = v.strip()
     checked = 0
     for name, info in sorted(rows.items()):
-        m = re.match(r"_ZN2pv18k_synthesis_lockedILi(\d+)ELi(\d)ELb([01])E", name)
-        assert m, name
+        # k_synthesis<L, MODE = kModeLocked (6), DT, QPOW2, LANEK = false, NR = L / 64>
+        m = re.match(r"_ZN2pv11k_synthesisILi(\d+)ELi6ELi(\d)ELb([01])ELb0ELi(\d+)EE", name)
+        assert m and int(m.group(4)) * 64 == int(m.group(1)), name
         print(f"L={m.group(1)} DT={m.group(2)} QPOW2={m.group(3)}: VGPRs {info['VGPRs']} AGPRs {info['AGPRs']} "
               f"spill {info['VGPRs Spill']} occupancy {info['Occupancy [waves/SIMD]']}")
         if int(m.group(1)) == 512 and int(m.group(2)) > 0:

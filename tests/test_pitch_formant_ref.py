@@ -141,8 +141,8 @@ def test_pitch_formant_symbols_and_null_handle():
 
 @pytest.mark.slow
 def test_warp_kernels_have_no_spills(tmp_path):
-    """pv_warp.hip for gfx950 with the Makefile's device flags: the 40 k_synthesis_warp
-    instantiations (4 sizes x {ring, 3 register overlap-add} + 4 generic-q rings, unlocked and
+    """pv_warp.hip for gfx950 with the Makefile's device flags: the 40 instantiations
+    of k_synthesis in the warp and the locked warp mode (4 sizes x {ring, 3 register overlap-add} + 4 generic-q rings, unlocked and
     locked) spill no VGPR and use no scratch."""
     out = str(tmp_path / "pv_warp.s")
     r = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off",
@@ -162,11 +162,14 @@ def test_warp_kernels_have_no_spills(tmp_path):
         elif cur and ":" in body:
             k, v = body.split(":", 1)
             rows[cur][k.strip()] = v.strip()
+    per_mode = {8: 0, 9: 0}
     for name, info in sorted(rows.items()):
-        m = re.match(r"_ZN2pv16k_synthesis_warpILi(\d+)ELb([01])ELi(\d)ELb([01])E", name)
-        assert m, name
-        print(f"L={m.group(1)} LOCK={m.group(2)} DT={m.group(3)} QPOW2={m.group(4)}: VGPRs {info['VGPRs']} "
+        # k_synthesis<L, MODE = kModeWarp (8) / kModeLockedWarp (9), DT, QPOW2, LANEK = false, NR = L / 64>
+        m = re.match(r"_ZN2pv11k_synthesisILi(\d+)ELi([89])ELi(\d)ELb([01])ELb0ELi(\d+)EE", name)
+        assert m and int(m.group(5)) * 64 == int(m.group(1)), name
+        per_mode[int(m.group(2))] += 1
+        print(f"L={m.group(1)} MODE={m.group(2)} DT={m.group(3)} QPOW2={m.group(4)}: VGPRs {info['VGPRs']} "
               f"AGPRs {info['AGPRs']} spill {info['VGPRs Spill']} scratch {info['ScratchSize [bytes/lane]']} "
               f"occupancy {info['Occupancy [waves/SIMD]']}")
         assert info["VGPRs Spill"] == "0" and info["ScratchSize [bytes/lane]"] == "0", (name, info)
-    assert len(rows) == 40
+    assert len(rows) == 40 and per_mode == {8: 20, 9: 20}
