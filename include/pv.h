@@ -404,6 +404,61 @@ pv_status pv_pitch_process(pv_handle* h, const float* x, long long ldx, long lon
 pv_status pv_pitch_set_formant(pv_handle* h, int order);
 int pv_pitch_get_formant(const pv_handle* h);
 
+/* Transient phase reset of the STANDARD time stretch.  The phase vocoder
+ * advances every bin's output phase from the bin's own history; at a drum hit, a click or a
+ * consonant that history says nothing about the new event, the bins of the attack frame no
+ * longer line up, and the attack smears over a whole window.  With the feature on, a flagged
+ * frame t0 is put down with its analysis phases (its waveform is the input's), and the frames
+ * after it keep the offset that made it so: with closed(t)[k] the output phase of the plain
+ * stretch,
+ *   phi_s(t0)[k] = phi(t0)[k]
+ *   phi_s(t)[k]  = closed(t)[k] + 2 pi Theta[k],  Theta[k] = frac((phi(t0)[k] - closed(t0)[k]) / 2 pi),
+ * until the next flagged frame; Theta = 0 before the first one.  The unwrap decisions, the run
+ * records and the carries are unchanged.  With pv_set_phase_lock on, a peak's output phase
+ * includes its Theta and the locking is otherwise unchanged; at a flagged frame Y = X.  With no
+ * frame flagged the output is the feature-off output of the split path bit for bit.
+ *   PV_TRANSIENT_OFF     (default)
+ *   PV_TRANSIENT_FLAGS   the frames flagged by pv_transient_set_flags
+ *   PV_TRANSIENT_DETECT  the frames the detector flags in every pv_process call: with, per
+ *       channel and frame, rise[t] = sum over bins 0 .. N/2 of max(0, mag_t[k] - mag_{t-1}[k])
+ *       (mag_{-1} = 0) and tot[t] = sum of mag_t[k] (fp32 sums in the kernel's order; a NaN
+ *       magnitude adds 0 to both), frame t >= 1 is flagged iff rise[t] > thr tot[t] and
+ *       rise[t] > rise[t-1] and rise[t] >= rise[t+1] (rise[frames] = 0): the local maximum of
+ *       the incoming energy inside a run of candidate frames.  The flags of the last call can be
+ *       read with pv_transient_get_flags.
+ * thr in (0, 1), or 0 for PV_TRANSIENT_DEFAULT_THRESHOLD.  Frame 0 is never flagged.
+ * pv_set_transient is a setup call (not capturable), ordered like the handle's compute calls.
+ * While the mode is not OFF, pv_process and pv_pitch_process run the reset synthesis (DETECT:
+ * analysis, onset, pick, carry, reset, synthesis; profile names onset, pick, reset,
+ * synthesis_reset); a single-launch handle takes the split path (pv_info.single_launch reads 0,
+ * pv_process(spec = NULL) uses the handle's own rows: pv_reserve_spectrum).
+ * pv_transient_reserve allocates, once and zeroed, the handle's flags (max_channels x max_frames
+ * bytes), the {rise, tot} rows (8 bytes per frame), the reset offsets (max_channels x runs x
+ * (N/2 + 1 padded) floats) and a word per run; PV_ERR_NOMEM if that fails.  It is not
+ * capturable; the first pv_process / pv_transient_set_flags call without it allocates them, and
+ * under a stream capture returns PV_ERR_ARG instead.
+ * pv_transient_set_flags / _get_flags: device pointers, flags[c*ld + t] (a byte, != 0: flagged),
+ * c < channels, t < frames, copied on `stream` (asynchronous, capturable once reserved); set
+ * clears the rest of those channels' rows and frame 0's flag.
+ * pv_onset_strength: dst[c*ld_dst + t] = {rise[t], tot[t]} of analysed frames, by the
+ * detector's kernel; any STANDARD handle, natural or packed rows; no state, capturable.
+ * Refusals, all PV_ERR_ARG with a pv_last_error text: a REF_COMPAT handle; a PV_PITCH_SHIFT
+ * handle; pv_set_transient (mode not OFF) while pv_pitch_set_formant is on, and
+ * pv_set_formant / pv_pitch_set_formant (order > 0) while the mode is not OFF; pv_segment_summary
+ * and pv_segment_resynthesis while the mode is not OFF; pv_resynthesis while the mode is not
+ * OFF; an unknown mode; thr outside (0, 1).  pv_rt and the harmoniser have no such switch. */
+enum { PV_TRANSIENT_OFF = 0, PV_TRANSIENT_FLAGS = 1, PV_TRANSIENT_DETECT = 2 };
+#define PV_TRANSIENT_DEFAULT_THRESHOLD 0.3f
+pv_status pv_transient_reserve(pv_handle* h);
+pv_status pv_set_transient(pv_handle* h, int mode, float thr);
+int pv_get_transient(const pv_handle* h);
+pv_status pv_transient_set_flags(pv_handle* h, const unsigned char* flags, long long ld, int channels,
+                                 int frames, void* stream);
+pv_status pv_transient_get_flags(pv_handle* h, unsigned char* flags, long long ld, int channels, int frames,
+                                 void* stream);
+pv_status pv_onset_strength(pv_handle* h, const pv_float2* spec, long long ld_spec, int channels, int frames,
+                            pv_float2* dst, long long ld_dst, void* stream);
+
 /* ---------------------------------------------------------------- real-time mode
  * A pv_rt streams `channels` mono channels through the STANDARD pipeline one callback at a
  * time.  State (input history, previous phases, unwrap counts, overlap accumulator) lives

@@ -136,6 +136,12 @@ pv_status do_resynthesis(pv_handle* h, const pv_float2* spec, long long ld_spec,
     // q = 1 (e.g. pitch 2.0): the output phase rho (phi + 2 pi M) is independent of the
     // unwrap count M mod 1, so no scan is needed
     const bool need_scan = h->mode == PV_MODE_STANDARD && (h->q > 1 || force_scan);
+    if (h->transient) {  // (STANDARD + PV_TIME_SHIFT: pv_set_transient)
+        if (seg || carry_from || ola_in)
+            return fail(PV_ERR_ARG, "transient phase reset: pv_process and pv_pitch_process only");
+        if ((st = transient_ready(h, "pv_process", s)) != PV_OK) return st;
+        if ((st = transient_flags(h, spec, ld_spec, C, frames, s)) != PV_OK) return st;
+    }
     if (need_scan && carry_from == nullptr) {
         pv::ScanParams sc = scan_params(h, spec, ld_spec, frames);
         sc.carry = h->d_carry;
@@ -179,7 +185,10 @@ pv_status do_resynthesis(pv_handle* h, const pv_float2* spec, long long ld_spec,
     p.src_hi = h->src_hi;
     p.t_off = seg ? seg->t_off : 0u;
     const int smode = (h->mode == PV_MODE_REF_COMPAT) ? 1 : (h->pitch ? 2 : 0);
-    if (h->formant) {  // (STANDARD + PV_PITCH_SHIFT: pv_set_formant)
+    if (h->transient) {
+        if ((st = transient_offsets(h, spec, ld_spec, C, frames, p.carry, &p, s)) != PV_OK) return st;
+        PV_LAUNCH(h, KSR, s, pv::launch_synthesis_reset(h->L_syn, h->phase_lock, C, p, s));
+    } else if (h->formant) {  // (STANDARD + PV_PITCH_SHIFT: pv_set_formant)
         const float* env = env_from ? env_from : h->d_env.p;
         if (!env) return fail(PV_ERR_ARG, "formant preservation is on but the handle has no envelope rows");
         const long long ld_env = (long long)h->cfg.max_frames * h->env_stride;
@@ -324,6 +333,8 @@ pv_status reserve_env_rows(pv_handle* h, const char* fn) {
 
 pv_status set_formant(pv_handle* h, int order, bool own_rows) {
     if (!h) return fail(PV_ERR_ARG, "null handle");
+    if (order > 0 && h->transient)
+        return fail(PV_ERR_ARG, "pv_set_formant: not while the transient phase reset is on (pv_set_transient)");
     if (h->mode != PV_MODE_STANDARD || h->effect != PV_PITCH_SHIFT)
         return fail(PV_ERR_UNSUPPORTED, "pv_set_formant: STANDARD pitch-shift handles only");
     if (order < 0 || order > h->N / 4) return fail(PV_ERR_ARG, "pv_set_formant: order must be in [0, N/4]");
@@ -390,6 +401,7 @@ pv_status pv_resynthesis(pv_handle* h, const pv_float2* spec, long long ld_spec,
                          long long ldo, void* stream) {
     pv_status st = check_common(h, channels, frames);
     if (st != PV_OK) return st;
+    if (h->transient) return fail(PV_ERR_ARG, "pv_resynthesis: not while the transient phase reset is on (pv_set_transient)");
     DeviceGuard g(h->cfg.device);
     ProfCall pc_(h);
     return do_resynthesis(h, spec, ld_spec, channels, frames, ola_in, ld_ola, out, ldo, false,
@@ -406,6 +418,7 @@ pv_status pv_segment_summary(pv_handle* h, const pv_float2* spec, long long ld_s
     pv_status st = check_common(h, channels, frames);
     if (st != PV_OK) return st;
     if (h->mode != PV_MODE_STANDARD) return fail(PV_ERR_UNSUPPORTED, "pv_segment_summary: STANDARD handles only");
+    if (h->transient) return fail(PV_ERR_ARG, "pv_segment_summary: not while the transient phase reset is on (pv_set_transient)");
     if (channels == 0) return PV_OK;
     if (!summary) return fail(PV_ERR_ARG, "null summary");
     // (an empty segment has no first or last phase: the caller leaves it out of the order)
@@ -435,6 +448,8 @@ pv_status pv_segment_resynthesis(pv_handle* h, const pv_float2* spec, long long 
     pv_status st = check_common(h, channels, frames);
     if (st != PV_OK) return st;
     if (frame0 < 0 || seg < 0) return fail(PV_ERR_ARG, "negative frame0 / seg");
+    if (h->transient)
+        return fail(PV_ERR_ARG, "pv_segment_resynthesis: not while the transient phase reset is on (pv_set_transient)");
     if (seg > 0 && !summaries) return fail(PV_ERR_ARG, "null summaries");
     if (channels == 0 || frames == 0) return PV_OK;
     DeviceGuard g(h->cfg.device);
@@ -486,6 +501,8 @@ pv_status pv_pitch_set_formant(pv_handle* h, int order) {
     pv_status st = check_std_stretch("pv_pitch_set_formant", h);
     if (st != PV_OK) return st;
     if (order < 0 || order > h->N / 4) return fail(PV_ERR_ARG, "pv_pitch_set_formant: order must be in [0, N/4]");
+    if (order > 0 && h->transient)
+        return fail(PV_ERR_ARG, "pv_pitch_set_formant: not while the transient phase reset is on (pv_set_transient)");
     if (order > 0) {
         // on a failure the feature stays as it was (off, on a first call)
         if ((st = reserve_env_rows(h, "pv_pitch_set_formant")) != PV_OK) return st;

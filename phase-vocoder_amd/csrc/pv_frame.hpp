@@ -7,6 +7,7 @@
 #include "pv_lock.hpp"
 #include "pv_formant.hpp"
 #include "pv_warp.hpp"
+#include "pv_transient.hpp"
 
 
 namespace pv {
@@ -233,7 +234,9 @@ struct SynLds {
 // locking (pv_lock.hpp), MODE 7 (kModeFormant): MODE 2 with the formant gather of
 // pv_formant.hpp (env: the frame's log envelope row), MODE 8 / 9 (kModeWarp / kModeLockedWarp):
 // MODE 0 / kModeLocked with the envelope warp of pv_warp.hpp on the magnitudes (env as in MODE 7;
-// tb.srcl: the warp map).  tq = (t + 1) mod q.
+// tb.srcl: the warp map), MODE 10 / 11 (kModeReset / kModeLockedReset): MODE 0 / kModeLocked with
+// the transient phase reset of pv_transient.hpp (rst: the wave's Theta registers and the frame's
+// flag).  tq = (t + 1) mod q.
 // Result: STORE_LAST: time samples in tile (natural order, padded); else the inverse
 // FFT's last-pass registers z (point lane + 64 last_slot(idx)).
 // QPOW2: the output-phase denominator q is a power of two <= 2^24 (compile-time path);
@@ -266,7 +269,7 @@ struct TwReg {
 // what the RACC path computes with q = 1 (R = tj = +0).
 template <int L, int MODE, bool STORE_LAST, bool QPOW2 = false, bool KREG = false, bool RACC = false,
           bool Q1 = false, typename Hook = NoHook, typename TwS = NoTwReg, bool V3X = false,
-          typename Env = NoEnv>
+          typename Env = NoEnv, typename Rst = NoReset>
 __device__ __forceinline__ void synth_frame(const float2 (&sv)[Geo<L>::E + 1], bool add_decision,
                                             unsigned tq, int (&M)[Geo<L>::E + 1],
                                             float (&phprev)[Geo<L>::E + 1], const PhaseMap& pm,
@@ -275,7 +278,7 @@ __device__ __forceinline__ void synth_frame(const float2 (&sv)[Geo<L>::E + 1], b
                                             const float (&ekr)[Geo<L>::E + 1],
                                             const unsigned (&jkr)[Geo<L>::E + 1],
                                             const Hook& hook = Hook{}, const TwS& twr = TwS{},
-                                            const Env& env = Env{}) {
+                                            const Env& env = Env{}, const Rst& rst = Rst{}) {
     using G_ = Geo<L>;
     constexpr int E = G_::E;
     constexpr int B = L + 1;
@@ -313,6 +316,12 @@ __device__ __forceinline__ void synth_frame(const float2 (&sv)[Geo<L>::E + 1], b
         static_assert(!(LOCKED && Q1), "the locked synthesis has no Q1 form");
         static_assert(!mode_is_warp(MODE) || (Env::ON && !Q1), "the envelope warp needs the envelope row");
         const float rrev = LOCKED ? pm.rho_rev - kInv2Pi : pm.rho_rev;
+        // reset modes (pv_transient.hpp), unlocked: the additive part of phc, for the locked form
+        // of a flagged frame
+        static_assert(Rst::ON == mode_is_reset(MODE) && !(Rst::ON && Q1), "the reset state goes with the reset modes");
+        constexpr bool ROFF = Rst::ON && !LOCKED;
+        float off[ROFF ? E + 1 : 1];
+        (void)off;
         if constexpr (Q1) {
             PV_FOR_BINS(E, lane, { phc[i] = __builtin_fmaf(pm.rho_rev, ph[i], 0.0f); })
         } else if constexpr (RACC) {
@@ -330,6 +339,7 @@ __device__ __forceinline__ void synth_frame(const float2 (&sv)[Geo<L>::E + 1], b
                 phprev[i] = ph[i];
                 const float tj = __builtin_amdgcn_fractf(tqf * __uint_as_float(jkv[i]));
                 phc[i] = __builtin_fmaf(rrev, ph[i], R + tj);
+                if constexpr (ROFF) off[i] = R + tj;
             })
         } else {
         PV_FOR_BINS(E, lane, {
@@ -346,11 +356,13 @@ __device__ __forceinline__ void synth_frame(const float2 (&sv)[Geo<L>::E + 1], b
             PV_FOR_BINS(E, lane, {
                 const unsigned x = __umul24(pmod, (unsigned)M[i] & (qq - 1u)) + __umul24(tq, jkv[i]);
                 phc[i] = __builtin_fmaf(rrev, ph[i], (float)(x & (qq - 1u)) * pm.inv_q);
+                if constexpr (ROFF) off[i] = (float)(x & (qq - 1u)) * pm.inv_q;
             })
         } else if (pm.q_pow2) {
             PV_FOR_BINS(E, lane, {
                 const unsigned x = pmod * ((unsigned)M[i] & (qq - 1u)) + tq * jkv[i];
                 phc[i] = __builtin_fmaf(rrev, ph[i], (float)(x & (qq - 1u)) * pm.inv_q);
+                if constexpr (ROFF) off[i] = (float)(x & (qq - 1u)) * pm.inv_q;
             })
         } else {
             PV_FOR_BINS(E, lane, {
@@ -358,9 +370,26 @@ __device__ __forceinline__ void synth_frame(const float2 (&sv)[Geo<L>::E + 1], b
                 mdq += (mdq < 0) ? (int)qq : 0;
                 const unsigned x = pmod * (unsigned)mdq + tq * jkv[i];
                 phc[i] = __builtin_fmaf(rrev, ph[i], (float)(x % qq) * pm.inv_q);
+                if constexpr (ROFF) off[i] = (float)(x % qq) * pm.inv_q;
             })
         }
         }  // !RACC
+        // transient phase reset: a flagged frame (wave-uniform: a scalar branch)
+        // replaces Theta by minus the locked form of its phase, and every frame adds Theta — the
+        // flagged frame so lands on its analysis phase, up to whole revolutions
+        if constexpr (Rst::ON) {
+            if (rst.flag) {
+                const float rrl = pm.rho_rev - kInv2Pi;
+                (void)rrl;
+                PV_FOR_BINS(E, lane, {
+                    float lf;
+                    if constexpr (LOCKED) lf = phc[i];
+                    else lf = __builtin_fmaf(rrl, ph[i], off[i]);
+                    rst.th[i] = reset_offset(lf);
+                })
+            }
+            PV_FOR_BINS(E, lane, { phc[i] += rst.th[i]; })
+        }
         // (PV_ABL_*: diagnostic ablations for A/B timing only — wrong results)
 #ifdef PV_ABL_NOGATHER
         if constexpr (false) {

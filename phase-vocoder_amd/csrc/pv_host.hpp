@@ -30,11 +30,11 @@ pv_status fail(pv_status s, const std::string& msg);
     } while (0)
 
 // kernel ids of the per-launch profile and their names (pv_profile_read), index for index
-enum { KA, KRS, KC, KS, KSEAM, KCA, KRT, KF, KSL, KENV, KSF, KRES, KRTR, KSW, kNumKernels };
+enum { KA, KRS, KC, KS, KSEAM, KCA, KRT, KF, KSL, KENV, KSF, KRES, KRTR, KSW, KON, KPK, KRST, KSR, kNumKernels };
 inline constexpr const char* kKernelNames[] = {"analysis", "runsum", "carry", "synthesis", "seam",
                                                "compat_analysis", "rt", "fused", "synthesis_locked",
                                                "envelope", "synthesis_formant", "resample", "rt_resample",
-                                               "synthesis_warp"};
+                                               "synthesis_warp", "onset", "pick", "reset", "synthesis_reset"};
 static_assert(sizeof(kKernelNames) / sizeof(kKernelNames[0]) == kNumKernels, "one name per kernel id");
 
 // Move-only owner of one hipMalloc (Pinned: hipHostMalloc, device-mapped) allocation.  Converts
@@ -134,6 +134,17 @@ struct pv_handle {
     pv_resampler* pitch_rs = nullptr;
     pvhost::DevBuf<float> d_pitch;
     long long ld_pitch = 0;
+    // pv_set_transient: the transient phase reset of the time stretch (PV_TRANSIENT_*), the
+    // detector's threshold, and the buffers of pv_transient_reserve (allocated once, zeroed):
+    // flags [max_channels][max_frames] bytes, {rise, tot} [max_channels][max_frames], Theta
+    // [max_channels][max_runs][bins_pad], prev_reset_run [max_channels][max_runs]
+    int transient = 0;
+    float transient_thr = PV_TRANSIENT_DEFAULT_THRESHOLD;
+    pvhost::DevBuf<unsigned char> d_tr_flags;
+    pvhost::DevBuf<float2> d_tr_strength;
+    pvhost::DevBuf<float> d_tr_theta;
+    pvhost::DevBuf<int> d_tr_prr;
+    std::mutex tr_mu;
     float scale = 1.0f, rho = 1.0f, inv_q = 1.0f;
     unsigned long long p_mod = 0, q = 1;
     int q_pow2 = 1;
@@ -251,10 +262,10 @@ pv_status check_std_stretch(const char* fn, const pv_handle* h);
 inline int nruns_of(const pv_handle* h, int frames) { return (frames + h->F - 1) / h->F; }
 // the analysis keeps e_k in a register per lane (k_std_analysis EK_LANE)
 inline bool ek_lane_of(int hop_div, int bins) { return 64 % hop_div == 0 && bins >= 64; }
-// the single launch serves the handle's pv_process calls (phase locking, formant preservation
-// and the envelope warp run on the split path)
+// the single launch serves the handle's pv_process calls (phase locking, formant preservation,
+// the envelope warp and the transient phase reset run on the split path)
 inline bool single_launch(const pv_handle* h) {
-    return h->F_fused > 0 && !h->phase_lock && !h->formant && !h->pitch_formant;
+    return h->F_fused > 0 && !h->phase_lock && !h->formant && !h->pitch_formant && !h->transient;
 }
 
 // ---- launch sequences (pv_api_batch.cpp)
@@ -279,6 +290,16 @@ pv_status process_impl(pv_handle* h, const float* x, long long ldx, long long n_
                        pv_float2* spec, long long ld_spec, float* out, long long ldo, hipStream_t s);
 // own_rows: allocate the handle's envelope rows (a harmoniser's voices k > 0 read voice 0's)
 pv_status set_formant(pv_handle* h, int order, bool own_rows);
+
+// ---- transient phase reset (pv_api_transient.cpp)
+// the handle's transient buffers exist, or are allocated now (refused while s is being captured)
+pv_status transient_ready(pv_handle* h, const char* fn, hipStream_t s);
+// do_resynthesis with the feature on: before the carries, the flags (k_onset + k_pick, or
+// k_pick's run scan on the caller's flags) ...
+pv_status transient_flags(pv_handle* h, const pv_float2* spec, long long ld_spec, int C, int frames, hipStream_t s);
+// ... and after them, Theta of the flagged runs (k_reset) and the reset fields of the synthesis
+pv_status transient_offsets(pv_handle* h, const pv_float2* spec, long long ld_spec, int C, int frames,
+                            const int* carry, pv::SynParams* p, hipStream_t s);
 
 // ---- resampler (pv_api_resample.cpp)
 // the launch of pv_resample / pv_pitch_process (arguments checked by the caller)

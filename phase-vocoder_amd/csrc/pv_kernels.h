@@ -109,6 +109,71 @@ struct SynParams {
     const float* env;
     long long ld_env;
     int env_stride;
+    // k_synthesis in the reset modes (pv_transient.hip) has no pitch map and no envelope: its
+    // arguments travel in those fields (reset_args below), so the block keeps its size and
+    // layout and no other kernel's code changes
+};
+
+// The reset modes' view of SynParams: flags[c * ld_flags + t] != 0: frame t is a transient;
+// theta[(c * nruns + run) * bins_pad + k]: Theta after the run's last flagged frame (k_reset;
+// revolutions); prev_reset_run[c * nruns + run]: the last run below `run` that holds a flagged
+// frame, or -1 (k_pick).
+struct ResetArgs {
+    const unsigned char* flags;
+    long long ld_flags;
+    const float* theta;
+    const int* prev_reset_run;
+};
+__host__ __device__ inline ResetArgs reset_args(const SynParams& p) {
+    return ResetArgs{reinterpret_cast<const unsigned char*>(p.src_cnt), p.ld_env, p.env, p.src_first};
+}
+inline void set_reset_args(SynParams* p, const ResetArgs& a) {
+    p->src_cnt = reinterpret_cast<const int*>(a.flags);
+    p->ld_env = a.ld_flags;
+    p->env = a.theta;
+    p->src_first = a.prev_reset_run;
+}
+
+// transient detector and reset offsets (pv_transient.hip)
+// k_onset: dst[c * ld_dst + t] = {rise, tot} of frame t: rise = sum over bins 0 .. L of
+// max(0, mag_t[k] - mag_{t-1}[k]) (mag_{-1} = 0), tot = sum of mag_t[k]; fp32, the kernel's order
+struct OnsetParams {
+    const float2* spec;
+    long long ld_spec;
+    int spec_stride, frames, F, nruns;
+    int packed;                        // PV_SPEC_PACKED rows
+    float2* dst;
+    long long ld_dst;
+};
+// k_pick: flags from the strengths (strength != nullptr) — flag[t] = t >= 1 and rise[t] > thr
+// tot[t] and rise[t] > rise[t-1] and rise[t] >= rise[t+1] (rise[frames] = 0) — and, from the
+// flags, prev_reset_run
+struct PickParams {
+    const float2* strength;            // nullptr: the flags are the caller's, only the run scan
+    long long ld_strength;
+    float thr;
+    unsigned char* flags;
+    long long ld_flags;
+    int* prev_reset_run;               // [C][nruns]
+    int frames, F, nruns;
+};
+// k_reset: theta of every run that holds a flagged frame, from the run's carry and its rows up
+// to its last flagged frame
+struct ResetParams {
+    const float2* spec;
+    long long ld_spec;
+    int spec_stride, frames, F, nruns, bins_pad;
+    int packed;
+    const int* carry;                  // nullptr: q = 1, no unwrap state
+    const float* ek;
+    const unsigned* jk_mod;
+    float rho;
+    unsigned long long p_mod, q;
+    int q_pow2;
+    float inv_q;
+    const unsigned char* flags;
+    long long ld_flags;
+    float* theta;                      // [C][nruns][bins_pad]
 };
 
 // log spectral envelope of every frame (k_envelope, pv_formant.hip): the cepstrum of the
@@ -257,6 +322,15 @@ hipError_t launch_synthesis_formant(int L, int channels, const SynParams& p, hip
 // src_first / src_cnt carry the warp map {i_k} / {bits of f_k}, k <= L (a time stretch has no
 // pitch map; k_lane and src_hi are not used); same tails for launch_seam.  L <= 1024.
 hipError_t launch_synthesis_warp(int L, int lock, int channels, const SynParams& p, hipStream_t s);
+// STANDARD time stretch with the transient phase reset (pv_transient.hip; pv_set_transient):
+// launch_synthesis's mode 0, or launch_synthesis_locked with lock != 0, with Theta added to every
+// output phase (set_reset_args; k_lane and src_hi are not used); same
+// tails for launch_seam.  L <= 1024.  Before it: launch_onset and launch_pick (or launch_pick
+// alone on the caller's flags), the carries, launch_reset.
+hipError_t launch_onset(int L, int channels, const OnsetParams& p, hipStream_t s);
+hipError_t launch_pick(int channels, const PickParams& p, hipStream_t s);
+hipError_t launch_reset(int L, int channels, const ResetParams& p, hipStream_t s);
+hipError_t launch_synthesis_reset(int L, int lock, int channels, const SynParams& p, hipStream_t s);
 // the synthesis kernel for this geometry can take SynParams.k_lane (register overlap-add,
 // power-of-two q, STANDARD)
 bool synthesis_lane_kernel(int L, int mode, int hs, bool q_pow2, unsigned long long q);

@@ -21,6 +21,10 @@ namespace pv {
 //         with the envelope warp (pv_warp.hpp).  They add no state across frames: the unwrap
 //         state, the carries, the run records and the stream segments are the plain modes'.
 //         No per-lane-constant (LANEK) or partial-row (NR) variants.
+// kModeReset / kModeLockedReset: MODE 0 / kModeLocked with the transient phase reset
+//         (pv_transient.hpp): one more additive phase offset per bin, Theta, kept in the wave's
+//         registers — from the last flagged run before this one and replaced at the run's own
+//         flagged frames (reset_args, pv_kernels.h).
 // Overlap-add: a position is final once the frame that starts after it has been added;
 // final samples are stored straight to `out`.
 //   DT > 0 (out hop = 128 DT, L <= 1024): in registers.  After the inverse FFT's last pass
@@ -124,6 +128,21 @@ __global__ __launch_bounds__(256, (L <= 256) ? 4 : (L == 512) ? (MODE >= kModeLo
     }
     constexpr int NS = SynTraits<L, MODE, DT, QPOW2>::NS, D = SynTraits<L, MODE, DT, QPOW2>::D;
     float2 acc[NS];
+    if constexpr (mode_is_reset(MODE)) {
+        // Theta of the last flagged run before this one (k_reset wrote it), or 0; the run's own
+        // flagged frames replace it as the wave meets them
+        float th[E + 1];
+        int prr = -1;
+        const ResetArgs ra = reset_args(p);
+        if (nfr > 0) prr = __builtin_amdgcn_readfirstlane(ra.prev_reset_run[(long long)c * p.nruns + run]);
+        const float* ths = ra.theta + ((long long)c * p.nruns + (prr >= 0 ? prr : 0)) * p.bins_pad;
+#pragma unroll
+        for (int i = 0; i <= E; ++i) th[i] = 0.0f;
+        if (prr >= 0) { PV_FOR_BINS(E, lane, { th[i] = ths[k]; }) }
+        const ResetRun<E> rs{th, ra.flags + (long long)c * ra.ld_flags + t0};
+        syn_run<L, MODE, DT, QPOW2, LANEK, NR, ResetRun<E>>(
+            p, SynCarve{twl, twsl, tiles, rings, gainl, ekl, jkl, srcl}, tw0, lane, w, c, t0, nfr, M, phprev, acc, rs);
+    } else
     syn_run<L, MODE, DT, QPOW2, LANEK, NR>(
         p, SynCarve{twl, twsl, tiles, rings, gainl, ekl, jkl, srcl}, tw0, lane, w, c, t0, nfr, M, phprev, acc);
     if constexpr (ROLA) {

@@ -245,11 +245,13 @@ struct SynTraits {
 // pitch ratio > 1 only those some output bin takes its source from (src_hi) — the other slots
 // are never gathered, and without a spectrum output the analysis does not write them
 // (k_std_analysis NA): they stay zero in the registers, no load, no stale bytes read.
-template <int L, int MODE, int DT, bool QPOW2, bool LANEK = false, int NR = Geo<L>::E>
+// RS: the reset modes' state (ResetRun, pv_transient.hpp): the wave's Theta registers and the
+// run's flag bytes, read 64 frames at a time as one ballot (once per run for F <= 64).
+template <int L, int MODE, int DT, bool QPOW2, bool LANEK = false, int NR = Geo<L>::E, typename RS = NoResetRun>
 __device__ __forceinline__ void syn_run(const SynParams& p, const SynCarve& sc, const float2 (&tw0)[Geo<L>::E],
                                         int lane, int w, int c, int t0, int nfr,
                                         int (&M)[Geo<L>::E + 1], float (&phprev)[Geo<L>::E + 1],
-                                        float2 (&acc)[SynTraits<L, MODE, DT, QPOW2>::NS]) {
+                                        float2 (&acc)[SynTraits<L, MODE, DT, QPOW2>::NS], const RS& rs = RS{}) {
     using G_ = Geo<L>;
     using T_ = SynTraits<L, MODE, DT, QPOW2>;
     constexpr bool ROLA = T_::ROLA;
@@ -312,6 +314,9 @@ __device__ __forceinline__ void syn_run(const SynParams& p, const SynCarve& sc, 
         for (int q = 0; q < E; ++q) twr.v[q] = lds_ld(&sc.twsl[lane + 64 * q]);
     }
     const unsigned q32 = (unsigned)p.q;  // <= 2^24 (QPOW2) or <= 32768
+    static_assert(RS::ON == mode_is_reset(MODE), "the reset state goes with the reset modes");
+    unsigned long long flagw = 0;  // reset modes: the flags of frames 64 (u / 64) .. + 63 of the run
+    (void)flagw;
     // (env: the frame's log envelope row, formant and warp modes; NoEnv otherwise)
     auto synth = [&](int u, int t, const float2 (&sv)[E + 1], float2 (&z)[E], const auto& hk, const auto& env) {
         // (t_off: a segment's first frame index in its whole stream, mod q)
@@ -319,6 +324,15 @@ __device__ __forceinline__ void syn_run(const SynParams& p, const SynCarve& sc, 
         using H = std::decay_t<decltype(hk)>;
         using EV = std::decay_t<decltype(env)>;
         // (L = 1024: the radix-16/16/4 inverse FFT on the v3 pass table, p.tw)
+        if constexpr (RS::ON) {
+            if ((u & 63) == 0) {
+                const int uu = u + lane;
+                flagw = __builtin_amdgcn_ballot_w64(uu < nfr && rs.flags[uu < nfr ? uu : 0] != 0);
+            }
+            const ResetRef<E> rr{rs.th, ((flagw >> (u & 63)) & 1ull) != 0};
+            synth_frame<L, MODE, !ROLA, QPOW2, KREG, RACC, false, H, TwS, (L == 1024), EV, ResetRef<E>>(
+                sv, u > 0, tq, M, phprev, pmap, stb, tw0, tile, lane, z, ekr, jkr, hk, twr, env, rr);
+        } else
         synth_frame<L, MODE, !ROLA, QPOW2, KREG, RACC, false, H, TwS, (L == 1024), EV>(
             sv, u > 0, tq, M, phprev, pmap, stb, tw0, tile, lane, z, ekr, jkr, hk, twr, env);
     };

@@ -18,7 +18,9 @@ namespace pv {
 constexpr int kModeWarp = 8;
 constexpr int kModeLockedWarp = 9;
 constexpr bool mode_is_warp(int mode) { return mode == kModeWarp || mode == kModeLockedWarp; }
-constexpr bool mode_is_locked(int mode) { return mode == kModeLocked || mode == kModeLockedWarp; }
+constexpr bool mode_is_locked(int mode) {
+    return mode == kModeLocked || mode == kModeLockedWarp || mode == kModeLockedReset;
+}
 
 // A wave holds the frame: bin k = lane + 64 i in register slot i (i < E), bin L in slot E
 // (every lane holds le[L]; lane 0's is the one that counts).  le goes to wt[k] (LDS, L + 2

@@ -24,6 +24,11 @@
 //                                        --pitch-resample (--mode std, effect t); composes with
 //                                        --phase-lock; not with --rt.  For harmonic-rich signals:
 //                                        a lone sinusoid is its own envelope and is attenuated
+//     --transients [THR]                 transient phase reset at detected onsets (pv_set_transient,
+//                                        PV_TRANSIENT_DETECT; THR in (0, 1), the default without
+//                                        it): --mode std with effect t and --batched or
+//                                        --pitch-resample; composes with --phase-lock; not with
+//                                        --pitch-formant or --rt
 //     --single-arg                       PhaseVocoder(N): periodic Hann, hop N/2 (phaseVocoder.h:46-78)
 //     --nan-faithful                     atanf(0/0) = NaN phases as the reference (kernel.cu:101-109)
 //     --timer                            print CudaPhase::timer() per call (main.cpp:238-241, 275-278)
@@ -89,6 +94,8 @@ int main(int argc, char** argv) {
     float scale = 1.0f;
     bool batched = false, single_arg = false, show_timer = false, rt = false, phase_lock = false;
     int formant = 0, pitch_formant = 0;
+    bool transients = false;
+    float transient_thr = 0.0f;  // 0: PV_TRANSIENT_DEFAULT_THRESHOLD
     int pitch_resample = -1;  // --pitch-resample: quality preset (0 fast, 1 best)
     double ana_ms = 0.0, syn_ms = 0.0;
     pv_mode mode = PV_MODE_REF_COMPAT;
@@ -107,6 +114,18 @@ int main(int argc, char** argv) {
         else if (a == "--rt") rt = true;
         else if (a == "--phase-lock") phase_lock = true;
         else if (a == "--formant" && i + 1 < argc) formant = std::atoi(argv[++i]);
+        else if (a == "--transients") {
+            transients = true;
+            // (an optional threshold: the next argument if it reads as a number in (0, 1))
+            if (i + 1 < argc) {
+                char* end = nullptr;
+                const float v = std::strtof(argv[i + 1], &end);
+                if (end != argv[i + 1] && *end == 0 && v > 0.0f && v < 1.0f) {
+                    transient_thr = v;
+                    ++i;
+                }
+            }
+        }
         else if (a == "--pitch-formant" && i + 1 < argc) pitch_formant = std::atoi(argv[++i]);
         else if (a == "--pitch-resample" && i + 1 < argc) {
             const std::string q = argv[++i];
@@ -188,6 +207,17 @@ int main(int argc, char** argv) {
         }
         if (pv_pitch_set_formant(phase.handle, pitch_formant) != PV_OK) {
             std::fprintf(stderr, "err: --pitch-formant: %s\n", pv_last_error());
+            return 1;
+        }
+    }
+    if (transients) {
+        if (rt || !(batched || pitch_resample >= 0)) {
+            std::fprintf(stderr, "err: --transients needs --batched or --pitch-resample (not --rt)\n");
+            return 1;
+        }
+        if (pv_set_transient(phase.handle, PV_TRANSIENT_DETECT, transient_thr) != PV_OK ||
+            pv_transient_reserve(phase.handle) != PV_OK) {
+            std::fprintf(stderr, "err: --transients: %s\n", pv_last_error());
             return 1;
         }
     }

@@ -16,6 +16,8 @@ PV_TIME_SHIFT, PV_PITCH_SHIFT = ord("t"), ord("p")
 PV_MODE_REF_COMPAT, PV_MODE_STANDARD = 0, 1
 PV_WINDOW_DEFAULT, PV_WINDOW_HAMMING_REF, PV_WINDOW_HANN_REF = 0, 1, 2
 PV_SPEC_NATURAL, PV_SPEC_PACKED = 0, 1
+PV_TRANSIENT_OFF, PV_TRANSIENT_FLAGS, PV_TRANSIENT_DETECT = 0, 1, 2
+PV_TRANSIENT_DEFAULT_THRESHOLD = 0.3  # include/pv.h
 ABI_VERSION = 5  # PV_ABI_VERSION of include/pv.h (pv_config / pv_info lead with it)
 
 
@@ -208,6 +210,18 @@ def lib():
     L.pv_pitch_set_formant.restype = i
     L.pv_pitch_get_formant.argtypes = [vp]
     L.pv_pitch_get_formant.restype = i
+    L.pv_transient_reserve.argtypes = [vp]
+    L.pv_transient_reserve.restype = i
+    L.pv_set_transient.argtypes = [vp, i, f]
+    L.pv_set_transient.restype = i
+    L.pv_get_transient.argtypes = [vp]
+    L.pv_get_transient.restype = i
+    L.pv_transient_set_flags.argtypes = [vp, vp, ll, i, i, vp]
+    L.pv_transient_set_flags.restype = i
+    L.pv_transient_get_flags.argtypes = [vp, vp, ll, i, i, vp]
+    L.pv_transient_get_flags.restype = i
+    L.pv_onset_strength.argtypes = [vp, vp, ll, i, i, vp, ll, vp]
+    L.pv_onset_strength.restype = i
     _lib = L
     return L
 

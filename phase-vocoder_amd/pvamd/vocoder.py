@@ -44,7 +44,8 @@ class PhaseVocoder:
                  max_frames: int = 4096, device: int = 0, exit_on_error: bool = False,
                  window: int = _lib.PV_WINDOW_DEFAULT, nan_faithful: bool = False,
                  spec_layout: int = _lib.PV_SPEC_NATURAL, tables_external: bool = False,
-                 phase_lock: bool = False, formant: int = 0, pitch_formant: int = 0):
+                 phase_lock: bool = False, formant: int = 0, pitch_formant: int = 0,
+                 transients: str = "off", transient_threshold: float = 0.0):
         """window: PV_WINDOW_DEFAULT (the mode's), PV_WINDOW_HAMMING_REF or
         PV_WINDOW_HANN_REF (the 1-argument constructor's, phaseVocoder.h:64-66; see
         `single_arg`); nan_faithful: REF_COMPAT atanf(0/0) = NaN (kernel.cu:101-109);
@@ -54,7 +55,9 @@ class PhaseVocoder:
         identity phase locking (STANDARD time stretch only, see `set_phase_lock`); formant:
         lifter order of the formant-preserving pitch shift (STANDARD pitch shift only, see
         `set_formant`; 0 = off); pitch_formant: lifter order of the formant preservation of
-        `pitch_process` (STANDARD time stretch only, see `set_pitch_formant`; 0 = off)."""
+        `pitch_process` (STANDARD time stretch only, see `set_pitch_formant`; 0 = off);
+        transients / transient_threshold: the transient phase reset (STANDARD time stretch only,
+        see `set_transients`)."""
         self.exit_on_error = exit_on_error
         eff = effect if isinstance(effect, int) else ord(effect)
         m = PV_MODE_REF_COMPAT if mode == REF_COMPAT else PV_MODE_STANDARD
@@ -86,6 +89,8 @@ class PhaseVocoder:
             self.set_formant(formant)
         if pitch_formant:
             self.set_pitch_formant(pitch_formant)
+        if transients != "off":
+            self.set_transients(transients, transient_threshold)
 
     def _read_info(self):
         info = _lib.new_info()
@@ -107,6 +112,63 @@ class PhaseVocoder:
     @property
     def phase_lock(self) -> bool:
         return bool(self._L.pv_get_phase_lock(self._h))
+
+    _TRANSIENT_MODES = {"off": _lib.PV_TRANSIENT_OFF, "flags": _lib.PV_TRANSIENT_FLAGS,
+                        "detect": _lib.PV_TRANSIENT_DETECT}
+
+    def set_transients(self, mode: str = "detect", threshold: float = 0.0):
+        """pv_set_transient: the transient phase reset of the STANDARD time stretch — a flagged
+        frame is put down with its analysis phases (an attack keeps its shape instead of
+        smearing over a window) and the frames after it keep the offset that made it so.
+        "off"; "flags": the frames given to `set_transient_flags`; "detect": the frames the
+        onset detector flags in every `process` call (threshold in (0, 1), 0 = the default).
+        Composes with `set_phase_lock`.  Applies to the calls made after it (`process`,
+        `pitch_process`); a single-launch handle runs the split path while it is on."""
+        if mode not in self._TRANSIENT_MODES:
+            raise ValueError(f"transients must be one of {sorted(self._TRANSIENT_MODES)}")
+        self._call(self._L.pv_set_transient(self._h, self._TRANSIENT_MODES[mode], float(threshold)),
+                   "pv_set_transient")
+        self._read_info()
+
+    @property
+    def transients(self) -> str:
+        m = int(self._L.pv_get_transient(self._h))
+        return {v: k for k, v in self._TRANSIENT_MODES.items()}[m]
+
+    def reserve_transients(self):
+        """pv_transient_reserve: allocate (once, zeroed) the handle's flags, onset strengths and
+        reset offsets, so that the calls that use them can be captured into a graph."""
+        self._call(self._L.pv_transient_reserve(self._h), "pv_transient_reserve")
+
+    def set_transient_flags(self, flags, stream=None):
+        """pv_transient_set_flags: flags [C, frames] (or [frames]), nonzero = the frame is a
+        transient (any CUDA tensor; compared with 0).  Frame 0 is never flagged."""
+        torch = _torch()
+        f = self._as2d(flags)
+        f = (f != 0).to(torch.uint8).contiguous()
+        self._call(self._L.pv_transient_set_flags(self._h, _ptr(f), f.stride(0), f.shape[0], f.shape[1],
+                                                  self._stream(stream)), "pv_transient_set_flags")
+
+    def transient_flags(self, channels: int, frames: int, stream=None):
+        """pv_transient_get_flags: the handle's flags [channels, frames] uint8 — the caller's, or
+        in "detect" mode those of the last `process` call."""
+        torch = _torch()
+        f = torch.zeros((channels, frames), dtype=torch.uint8, device=f"cuda:{self.device}")
+        self._call(self._L.pv_transient_get_flags(self._h, _ptr(f), f.stride(0), channels, frames,
+                                                  self._stream(stream)), "pv_transient_get_flags")
+        return f
+
+    def onset_strength(self, spec, frames: int | None = None, stream=None):
+        """pv_onset_strength: spec [C, frames, spec_stride, 2] of a STANDARD handle -> [C, frames,
+        2] float32 {rise, tot}: the summed positive magnitude increments of every frame over the
+        frame before it, and the frame's summed magnitudes."""
+        torch = _torch()
+        C = spec.shape[0]
+        frames = spec.shape[1] if frames is None else frames
+        dst = torch.zeros((C, frames, 2), dtype=torch.float32, device=spec.device)
+        self._call(self._L.pv_onset_strength(self._h, _ptr(spec), spec.stride(0) // 2, C, frames, _ptr(dst),
+                                             dst.stride(0) // 2, self._stream(stream)), "pv_onset_strength")
+        return dst
 
     def set_formant(self, order: int):
         """pv_set_formant: formant-preserving STANDARD pitch shift — the frame's cepstral
