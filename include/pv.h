@@ -459,6 +459,55 @@ pv_status pv_transient_get_flags(pv_handle* h, unsigned char* flags, long long l
 pv_status pv_onset_strength(pv_handle* h, const pv_float2* spec, long long ld_spec, int channels, int frames,
                             pv_float2* dst, long long ld_dst, void* stream);
 
+/* Time-map stretch: an arbitrary, time-varying playback rate.  Output frame
+ * u < n_out is built at the fractional analysis position pos[u] (in frames; one map for all
+ * channels of a call) with the synthesis hop equal to the analysis hop, so a tempo curve, a ratio
+ * that is no multiple of 1/hop, a freeze (pos constant), a scrub and a reverse (pos decreasing)
+ * are all maps.  The handle: STANDARD + PV_TIME_SHIFT with out_hop == hop (scale 1), natural or
+ * packed rows, n_samps in [256, 2048]; the map replaces the scale.
+ *   Map.  Every pos[u] finite, >= 0 and < 2^30; need not be monotonic; 1 <= n_out <= max_frames.
+ *     Split once on the host (pv_timemap_split): i_u = (int)floor(pos[u]),
+ *     a_u = (float)(pos[u] - floor(pos[u])).  At process time max_u i_u <= frames - 1.
+ *   Phase as an integer.  For an analysed row's phase phi: t = phi * (1/2pi) (one fp32 multiply,
+ *     the synthesis' constant 0x1.45f306p-3f), P = ((uint32_t)(int32_t)rintf(t * 0x1p31f)) << 1:
+ *     a fraction of a turn in units of 2^-32 (the scaling is exact, nothing saturates, ties to even).
+ *   Propagation, per channel and bin, modulo 2^32:
+ *     Phi(0) = P(i_0),  Phi(u+1) = Phi(u) + Delta(i_u),
+ *     Delta(i) = P(i+1) - P(i) for i + 1 < frames,  Delta(frames-1) = 0.
+ *     The sum is exact and associative: the result does not depend on the run length.
+ *   Magnitude.  m(u)[k] = fmaf(a_u, mag(i_u+1)[k] - mag(i_u)[k], mag(i_u)[k]) in fp32; row
+ *     `frames`, one past the end, reads as magnitude 0 and is never loaded.
+ *   Output phase.  Psi = Phi(u); with pv_set_phase_lock on, peaks and owners by the locking's
+ *     rules on m(u), and Psi[k] = P(i_u)[k] + (Phi(u)[own] - P(i_u)[own]).
+ *   Frame.  Y[k] = m(u)[k] (cos, sin)(2 pi Psi[k] / 2^32), Im Y(0) = Im Y(N/2) = 0; the inverse
+ *     FFT, gain and overlap-add at `hop` are the handle's own.  Output length:
+ *     pv_output_length(h, n_out).  With pos[u] = u, Psi = P(u), locked or not: pv_process at
+ *     scale 1 up to the 2^-31-turn quantisation.
+ * pv_timemap_split: pure host, no handle, no GPU; PV_ERR_ARG on NULL, n <= 0 or a position that
+ *   is not finite, negative or >= 2^30.
+ * pv_timemap_set: validates, splits and uploads the map; a setup call (not capturable), ordered
+ *   like the handle's compute calls.  Its first call allocates, zeroed, the map (max_frames
+ *   entries) and the scan's run sums and carries (max_channels x runs x (N/2 + 1 padded) uint32
+ *   each); on PV_ERR_NOMEM the feature stays off.  n_out > max_frames: PV_ERR_ARG.
+ *   pv_timemap_set(h, NULL, 0) clears the map.
+ * pv_timemap_frames: n_out; 0 for a NULL handle or when no map is set.
+ * pv_timemap_process: pv_process's arguments and `spec` semantics (frames: the analysed frames;
+ *   spec = NULL uses the handle's own rows, pv_reserve_spectrum, never the single launch);
+ *   out rows of pv_output_length(h, pv_timemap_frames(h)) samples.  Capturable under pv_process's
+ *   conditions once a map is set.  Launches (and pv_profile_read names): analysis, map_sum,
+ *   map_carry, synthesis_map, seam.  channels = 0 does nothing and returns PV_OK.
+ * Refusals, each with a pv_last_error text: a NULL handle PV_ERR_ARG (0 from the count); a
+ *   REF_COMPAT handle, a PV_PITCH_SHIFT handle, out_hop != hop: PV_ERR_UNSUPPORTED; process before
+ *   a successful set, frames < 1 with channels > 0, max i_u > frames - 1, the transient mode not
+ *   OFF, pv_pitch_set_formant on: PV_ERR_ARG.
+ * pv_process and every other entry point are unchanged by a map. */
+pv_status pv_timemap_split(const double* pos, int n, int* idx, float* frac);
+pv_status pv_timemap_set(pv_handle* h, const double* pos, int n_out);
+int pv_timemap_frames(const pv_handle* h);
+pv_status pv_timemap_process(pv_handle* h, const float* x, long long ldx, long long n_samples, int channels,
+                             int frames, pv_float2* spec, long long ld_spec, float* out, long long ldo,
+                             void* stream);
+
 /* ---------------------------------------------------------------- real-time mode
  * A pv_rt streams `channels` mono channels through the STANDARD pipeline one callback at a
  * time.  State (input history, previous phases, unwrap counts, overlap accumulator) lives

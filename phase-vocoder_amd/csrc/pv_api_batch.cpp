@@ -116,49 +116,18 @@ pv_status do_envelope(pv_handle* h, const pv_float2* spec, long long ld_spec, in
     return PV_OK;
 }
 
-// carry_from: unwrap carries already scanned by another handle of the same analysis
-// geometry (the harmoniser's voices share one scan); nullptr = scan here.
-// env_from: envelope rows already computed by another handle of the same analysis (the
-// harmoniser's voices share voice 0's, as they share its carries); nullptr = computed here.
-pv_status do_resynthesis(pv_handle* h, const pv_float2* spec, long long ld_spec, int C, int frames,
-                         const float* ola_in, long long ld_ola, float* out, long long ldo, bool have_runsum,
-                         hipStream_t s, const int* carry_from, bool force_scan, const SegState* seg,
-                         const float* env_from) {
-    if (C == 0 || frames == 0) {
-        return PV_OK;
-    }
-    if (!spec || !out) return fail(PV_ERR_ARG, "null spec/out");
-    const long long olen = pv_output_length(h, frames);
-    if (C > 1 && ldo < olen) return fail(PV_ERR_ARG, "ldo < pv_output_length");
-    pv_status st = check_ld_spec(h, frames, ld_spec);
-    if (st != PV_OK) return st;
-    const int nruns = nruns_of(h, frames);
-    // q = 1 (e.g. pitch 2.0): the output phase rho (phi + 2 pi M) is independent of the
-    // unwrap count M mod 1, so no scan is needed (DESIGN.md §3.3)
-    const bool need_scan = h->mode == PV_MODE_STANDARD && (h->q > 1 || force_scan);
-    if (h->transient) {  // (STANDARD + PV_TIME_SHIFT: pv_set_transient)
-        if (seg || carry_from || ola_in)
-            return fail(PV_ERR_ARG, "transient phase reset: pv_process and pv_pitch_process only");
-        if ((st = transient_ready(h, "pv_process", s)) != PV_OK) return st;
-        if ((st = transient_flags(h, spec, ld_spec, C, frames, s)) != PV_OK) return st;
-    }
-    if (need_scan && carry_from == nullptr) {
-        pv::ScanParams sc = scan_params(h, spec, ld_spec, frames);
-        sc.carry = h->d_carry;
-        sc.carry_in = seg ? seg->carry_in : nullptr;
-        sc.phi_in = seg ? seg->phi_in : nullptr;
-        if (!have_runsum) PV_LAUNCH(h, KRS, s, pv::launch_runsum(C, sc, s));
-        PV_LAUNCH(h, KC, s, pv::launch_carry(C, sc, s));
-    }
+// what every k_synthesis launch of the handle shares (the carries, a segment's offset and a
+// mode's own arguments are the caller's)
+pv::SynParams syn_params(const pv_handle* h, const pv_float2* spec, long long ld_spec, int frames, float* out,
+                         long long ldo, long long olen) {
     pv::SynParams p{};
     p.spec = reinterpret_cast<const float2*>(spec);
     p.ld_spec = ld_spec;
     p.spec_stride = h->spec_stride;
     p.frames = frames;
     p.F = h->F;
-    p.nruns = nruns;
+    p.nruns = nruns_of(h, frames);
     p.bins_pad = h->bins_pad;
-    p.carry = carry_from ? carry_from : (need_scan ? h->d_carry.p : nullptr);
     p.ek = h->d_ek;
     p.jk_mod = h->d_jk_mod;
     p.src_first = h->d_src_first;
@@ -183,6 +152,66 @@ pv_status do_resynthesis(pv_handle* h, const pv_float2* spec, long long ld_spec,
     p.k_lane = h->k_lane;
     p.packed = h->packed;
     p.src_hi = h->src_hi;
+    return p;
+}
+
+// k_seam after a synthesis of `frames` frames: the workgroups' tails (and ola_in at 0)
+pv_status do_seam(pv_handle* h, int C, int frames, const float* ola_in, long long ld_ola, float* out, long long ldo,
+                  long long olen, hipStream_t s) {
+    const int nruns = nruns_of(h, frames);
+    const int nwg = (nruns + 3) / 4;
+    if (nwg <= 1 && ola_in == nullptr) return PV_OK;
+    pv::SeamParams sm{};
+    sm.out = out;
+    sm.ldo = ldo;
+    sm.out_len = olen;
+    sm.tails = h->d_tails;
+    sm.ola_in = ola_in;
+    sm.ld_ola = ld_ola;
+    sm.nruns = nruns;
+    sm.nwg = nwg;
+    sm.F = h->F;
+    sm.hs = h->hs;
+    sm.tail_len = h->tail_len;
+    PV_LAUNCH(h, KSEAM, s, pv::launch_seam(C, sm, s));
+    return PV_OK;
+}
+
+// carry_from: unwrap carries already scanned by another handle of the same analysis
+// geometry (the harmoniser's voices share one scan); nullptr = scan here.
+// env_from: envelope rows already computed by another handle of the same analysis (the
+// harmoniser's voices share voice 0's, as they share its carries); nullptr = computed here.
+pv_status do_resynthesis(pv_handle* h, const pv_float2* spec, long long ld_spec, int C, int frames,
+                         const float* ola_in, long long ld_ola, float* out, long long ldo, bool have_runsum,
+                         hipStream_t s, const int* carry_from, bool force_scan, const SegState* seg,
+                         const float* env_from) {
+    if (C == 0 || frames == 0) {
+        return PV_OK;
+    }
+    if (!spec || !out) return fail(PV_ERR_ARG, "null spec/out");
+    const long long olen = pv_output_length(h, frames);
+    if (C > 1 && ldo < olen) return fail(PV_ERR_ARG, "ldo < pv_output_length");
+    pv_status st = check_ld_spec(h, frames, ld_spec);
+    if (st != PV_OK) return st;
+    // q = 1 (e.g. pitch 2.0): the output phase rho (phi + 2 pi M) is independent of the
+    // unwrap count M mod 1, so no scan is needed (DESIGN.md §3.3)
+    const bool need_scan = h->mode == PV_MODE_STANDARD && (h->q > 1 || force_scan);
+    if (h->transient) {  // (STANDARD + PV_TIME_SHIFT: pv_set_transient)
+        if (seg || carry_from || ola_in)
+            return fail(PV_ERR_ARG, "transient phase reset: pv_process and pv_pitch_process only");
+        if ((st = transient_ready(h, "pv_process", s)) != PV_OK) return st;
+        if ((st = transient_flags(h, spec, ld_spec, C, frames, s)) != PV_OK) return st;
+    }
+    if (need_scan && carry_from == nullptr) {
+        pv::ScanParams sc = scan_params(h, spec, ld_spec, frames);
+        sc.carry = h->d_carry;
+        sc.carry_in = seg ? seg->carry_in : nullptr;
+        sc.phi_in = seg ? seg->phi_in : nullptr;
+        if (!have_runsum) PV_LAUNCH(h, KRS, s, pv::launch_runsum(C, sc, s));
+        PV_LAUNCH(h, KC, s, pv::launch_carry(C, sc, s));
+    }
+    pv::SynParams p = syn_params(h, spec, ld_spec, frames, out, ldo, olen);
+    p.carry = carry_from ? carry_from : (need_scan ? h->d_carry.p : nullptr);
     p.t_off = seg ? seg->t_off : 0u;
     const int smode = (h->mode == PV_MODE_REF_COMPAT) ? 1 : (h->pitch ? 2 : 0);
     if (h->transient) {
@@ -218,23 +247,7 @@ pv_status do_resynthesis(pv_handle* h, const pv_float2* spec, long long ld_spec,
         PV_LAUNCH(h, KSL, s, pv::launch_synthesis_locked(h->L_syn, C, p, s));
     else
         PV_LAUNCH(h, KS, s, pv::launch_synthesis(h->L_syn, smode, C, p, s));
-    const int nwg = (nruns + 3) / 4;
-    if (nwg > 1 || ola_in != nullptr) {
-        pv::SeamParams sm{};
-        sm.out = out;
-        sm.ldo = ldo;
-        sm.out_len = olen;
-        sm.tails = h->d_tails;
-        sm.ola_in = ola_in;
-        sm.ld_ola = ld_ola;
-        sm.nruns = nruns;
-        sm.nwg = nwg;
-        sm.F = h->F;
-        sm.hs = h->hs;
-        sm.tail_len = h->tail_len;
-        PV_LAUNCH(h, KSEAM, s, pv::launch_seam(C, sm, s));
-    }
-    return PV_OK;
+    return do_seam(h, C, frames, ola_in, ld_ola, out, ldo, olen, s);
 }
 
 // q = 1 (STANDARD): analysis, processing, resynthesis and every seam in one launch
@@ -309,6 +322,26 @@ pv_status reserve_spec_own(pv_handle* h) {
 }
 }  // namespace
 
+// a spec = NULL call on the split path: the handle's own rows, allocated now unless s is being
+// captured (an allocation cannot be captured: the rows must exist already then)
+pv_status own_spectrum(pv_handle* h, const char* fn, hipStream_t s, pv_float2** spec, long long* ld_spec) {
+    bool have;
+    {
+        std::lock_guard<std::mutex> lk(h->spec_mu);
+        have = h->d_spec_own.p != nullptr;
+    }
+    if (!have) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+            return fail(PV_ERR_ARG, std::string(fn) + "(spec = NULL) under stream capture: call pv_reserve_spectrum first");
+        pv_status st = reserve_spec_own(h);
+        if (st != PV_OK) return st;
+    }
+    *spec = h->d_spec_own;
+    *ld_spec = (long long)h->cfg.max_frames * h->spec_stride;
+    return PV_OK;
+}
+
 namespace {
 // the handle's envelope rows (pv_set_formant, pv_pitch_set_formant): allocated once, zeroed
 pv_status reserve_env_rows(pv_handle* h, const char* fn) {
@@ -355,20 +388,7 @@ pv_status process_impl(pv_handle* h, const float* x, long long ldx, long long n_
     // (pitch > 1) are not analysed
     int src_hi = -1;
     if (!spec && channels > 0 && frames > 0) {
-        bool have;
-        {
-            std::lock_guard<std::mutex> lk(h->spec_mu);
-            have = h->d_spec_own.p != nullptr;
-        }
-        if (!have) {
-            // an allocation cannot be captured: under capture the rows must exist already
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-                return fail(PV_ERR_ARG, "pv_process(spec = NULL) under stream capture: call pv_reserve_spectrum first");
-            if ((st = reserve_spec_own(h)) != PV_OK) return st;
-        }
-        spec = h->d_spec_own;
-        ld_spec = (long long)h->cfg.max_frames * h->spec_stride;
+        if ((st = own_spectrum(h, "pv_process", s, &spec, &ld_spec)) != PV_OK) return st;
         // (formant preservation: the envelope at the target bins reads every magnitude)
         if (h->mode == PV_MODE_STANDARD && !h->formant) src_hi = h->src_hi;
     }

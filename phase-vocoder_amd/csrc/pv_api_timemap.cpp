@@ -1,0 +1,146 @@
+// pv_api_timemap.cpp — the time-map stretch of libpv (pv_timemap_*): the
+// host split of the map, the handle's map and scan buffers, and the launch sequence of
+// pv_timemap_process (analysis, map_sum, map_carry, synthesis_map, seam).
+#include <algorithm>
+#include <vector>
+
+#include "pv_host.hpp"
+
+namespace pvhost {
+
+namespace {
+
+// a STANDARD time-stretch handle at scale 1 (out hop = hop), N = 256 .. 2048
+pv_status check_handle(const char* fn, const pv_handle* h) {
+    if (!h) return fail(PV_ERR_ARG, "null handle");
+    if (h->mode != PV_MODE_STANDARD)
+        return fail(PV_ERR_UNSUPPORTED, std::string(fn) + ": REF_COMPAT handle (the time map is the STANDARD time stretch's)");
+    if (h->effect != PV_TIME_SHIFT)
+        return fail(PV_ERR_UNSUPPORTED, std::string(fn) + ": PV_PITCH_SHIFT handle (the time map is the STANDARD time stretch's)");
+    if (h->hs != h->hop)
+        return fail(PV_ERR_UNSUPPORTED, std::string(fn) + ": out_hop != hop (the map replaces the scale: create the handle with scale 1)");
+    if (h->L_syn < 128 || h->L_syn > 1024)
+        return fail(PV_ERR_UNSUPPORTED, std::string(fn) + ": n_samps must be in [256, 2048]");
+    return PV_OK;
+}
+
+// the map and the scan's run sums and carries: allocated by the first pv_timemap_set, zeroed
+pv_status reserve(pv_handle* h) {
+    if (h->d_map) return PV_OK;
+    const size_t C = (size_t)std::max(h->cfg.max_channels, 1), T = (size_t)std::max(h->cfg.max_frames, 1);
+    const size_t R = (size_t)std::max(h->max_runs, 1);
+    DevBuf<pv::MapEntry> map;
+    DevBuf<unsigned> sum, carry;
+    if (map.alloc_zero(T) != hipSuccess || sum.alloc_zero(C * R * h->bins_pad) != hipSuccess ||
+        carry.alloc_zero(C * R * h->bins_pad) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(PV_ERR_NOMEM, "pv_timemap_set: the map, run sums and carries");
+    }
+    h->d_map_sum = std::move(sum);
+    h->d_map_carry = std::move(carry);
+    h->d_map = std::move(map);
+    return PV_OK;
+}
+
+}  // namespace
+
+}  // namespace pvhost
+
+using namespace pvhost;
+
+extern "C" {
+
+pv_status pv_timemap_split(const double* pos, int n, int* idx, float* frac) {
+    if (!pos || !idx || !frac) return fail(PV_ERR_ARG, "pv_timemap_split: null argument");
+    if (n <= 0) return fail(PV_ERR_ARG, "pv_timemap_split: n must be positive");
+    if (!timemap_split(pos, n, idx, frac))
+        return fail(PV_ERR_ARG, "pv_timemap_split: every position must be finite, >= 0 and < 2^30");
+    return PV_OK;
+}
+
+pv_status pv_timemap_set(pv_handle* h, const double* pos, int n_out) {
+    pv_status st = check_handle("pv_timemap_set", h);
+    if (st != PV_OK) return st;
+    DeviceGuard g(h->cfg.device);
+    if (!pos && n_out == 0) {  // clear (the calls enqueued before it have read their map)
+        h->map_n = 0;
+        h->map_imax = 0;
+        return PV_OK;
+    }
+    if (!pos) return fail(PV_ERR_ARG, "pv_timemap_set: null positions");
+    if (n_out < 1 || n_out > h->cfg.max_frames)
+        return fail(PV_ERR_ARG, "pv_timemap_set: n_out must be in [1, max_frames]");
+    std::vector<int> idx(n_out);
+    std::vector<float> frac(n_out);
+    if (!timemap_split(pos, n_out, idx.data(), frac.data()))
+        return fail(PV_ERR_ARG, "pv_timemap_set: every position must be finite, >= 0 and < 2^30");
+    std::vector<pv::MapEntry> map(n_out);
+    for (int u = 0; u < n_out; ++u) map[u] = pv::MapEntry{idx[u], frac[u]};
+    // ordered like the compute calls: the calls enqueued before this one (on any stream) have
+    // read the old map before the new one lands, and the first call's zeroing is complete
+    PV_HIP(hipDeviceSynchronize());
+    if ((st = reserve(h)) != PV_OK) return st;
+    PV_HIP(hipMemcpy(h->d_map, map.data(), sizeof(pv::MapEntry) * (size_t)n_out, hipMemcpyHostToDevice));
+    PV_HIP(hipDeviceSynchronize());
+    h->map_n = n_out;
+    h->map_imax = *std::max_element(idx.begin(), idx.end());
+    return PV_OK;
+}
+
+int pv_timemap_frames(const pv_handle* h) { return h ? h->map_n : 0; }
+
+pv_status pv_timemap_process(pv_handle* h, const float* x, long long ldx, long long n_samples, int channels,
+                             int frames, pv_float2* spec, long long ld_spec, float* out, long long ldo,
+                             void* stream) {
+    pv_status st = check_handle("pv_timemap_process", h);
+    if (st != PV_OK || (st = check_common(h, channels, frames)) != PV_OK) return st;
+    if (channels == 0) return PV_OK;
+    if (h->map_n < 1) return fail(PV_ERR_ARG, "pv_timemap_process: no map (pv_timemap_set first)");
+    if (h->transient)
+        return fail(PV_ERR_ARG, "pv_timemap_process: not while the transient phase reset is on (pv_set_transient)");
+    if (h->pitch_formant)
+        return fail(PV_ERR_ARG, "pv_timemap_process: not while the envelope warp is on (pv_pitch_set_formant)");
+    if (frames < 1) return fail(PV_ERR_ARG, "pv_timemap_process: frames must be at least 1");
+    // every row the kernels read, i_u and (for i_u < frames - 1) i_u + 1, is an analysed one
+    if (h->map_imax > frames - 1)
+        return fail(PV_ERR_ARG, "pv_timemap_process: the map reads past the last analysed frame (max floor(pos) > frames - 1)");
+    if (!x || !out) return fail(PV_ERR_ARG, "null x/out");
+    const int n_out = h->map_n;
+    const long long olen = pv_output_length(h, n_out);
+    if (channels > 1 && ldo < olen) return fail(PV_ERR_ARG, "ldo < pv_output_length(h, pv_timemap_frames(h))");
+    DeviceGuard g(h->cfg.device);
+    ProfCall pc_(h);
+    hipStream_t s = (hipStream_t)stream;
+    if (!spec && (st = own_spectrum(h, "pv_timemap_process", s, &spec, &ld_spec)) != PV_OK) return st;
+    // every bin analysed (a time stretch reads them all); no run records: the scan is the map's
+    if ((st = do_analysis(h, x, ldx, n_samples, channels, frames, spec, ld_spec, false, s)) != PV_OK) return st;
+
+    pv::MapScanParams m{};
+    m.spec = reinterpret_cast<const float2*>(spec);
+    m.ld_spec = ld_spec;
+    m.spec_stride = h->spec_stride;
+    m.aframes = frames;
+    m.frames = n_out;
+    m.F = h->F;
+    m.nruns = nruns_of(h, n_out);  // <= max_runs: n_out <= max_frames
+    m.L = h->L_syn;
+    m.bins_pad = h->bins_pad;
+    m.packed = h->packed;
+    m.map = h->d_map;
+    m.sum = h->d_map_sum;
+    m.carry = h->d_map_carry;
+    PV_LAUNCH(h, KMS, s, pv::launch_map_sum(channels, m, s));
+    PV_LAUNCH(h, KMC, s, pv::launch_map_carry(channels, m, s));
+
+    pv::SynParams p = syn_params(h, spec, ld_spec, n_out, out, ldo, olen);
+    p.carry = reinterpret_cast<const int*>(h->d_map_carry.p);
+    p.q = 1;  // no output-phase denominator: the phase is the integer sum itself
+    p.q_pow2 = 1;
+    p.p_mod = 0;
+    p.inv_q = 1.0f;
+    pv::set_map_args(&p, pv::MapArgs{h->d_map, frames});
+    PV_LAUNCH(h, KSM, s, pv::launch_synthesis_map(h->L_syn, h->phase_lock, channels, p, s));
+    return do_seam(h, channels, n_out, nullptr, 0, out, ldo, olen, s);
+}
+
+}  // extern "C"

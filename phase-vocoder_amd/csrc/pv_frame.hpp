@@ -8,6 +8,7 @@
 #include "pv_formant.hpp"
 #include "pv_warp.hpp"
 #include "pv_transient.hpp"
+#include "pv_timemap.hpp"
 
 
 namespace pv {
@@ -236,7 +237,9 @@ struct SynLds {
 // MODE 0 / kModeLocked with the envelope warp of pv_warp.hpp on the magnitudes (env as in MODE 7;
 // tb.srcl: the warp map), MODE 10 / 11 (kModeReset / kModeLockedReset): MODE 0 / kModeLocked with
 // the transient phase reset of pv_transient.hpp (rst: the wave's Theta registers and the frame's
-// flag).  tq = (t + 1) mod q.
+// flag), MODE 12 / 13 (kModeMap / kModeLockedMap): the time-map stretch of pv_timemap.hpp — sv is
+// {the frame's interpolated magnitude, the bits of P(i_u)} and M holds Phi(u), both 32-bit
+// fractions of a turn; no unwrap state, e_k or j_k is read.  tq = (t + 1) mod q.
 // Result: STORE_LAST: time samples in tile (natural order, padded); else the inverse
 // FFT's last-pass registers z (point lane + 64 last_slot(idx)).
 // QPOW2: the output-phase denominator q is a power of two <= 2^24 (compile-time path);
@@ -297,6 +300,27 @@ __device__ __forceinline__ void synth_frame(const float2 (&sv)[Geo<L>::E + 1], b
         PV_FOR_BINS(E, lane, {
             float2 y = sv[i];
             if (k == 0 || k == L) y.y = 0.0f;  // C2R ignores Im of DC and Nyquist
+            Yr[i] = y;
+        })
+    } else if constexpr (mode_is_map(MODE)) {
+        // DESIGN.md §3.12.  Unlocked: Psi = Phi(u).  Locked: the rotation Phi(u) - P(i_u) of the
+        // peak that owns the bin goes through lock_offsets' LDS round trip as bits (no arithmetic
+        // on them as floats); the integer sum P(i_u) + rotation is made on the way back.
+        unsigned psi[E + 1];
+        if constexpr (MODE == kModeLockedMap) {
+            float rot[E + 1], own[E + 1];
+            rot[E] = 0.0f;
+            PV_FOR_BINS(E, lane, { rot[i] = __uint_as_float((unsigned)M[i] - __float_as_uint(ph[i])); })
+            lock_offsets<L>(mag, rot, lane, reinterpret_cast<float*>(tile), own);
+            PV_FOR_BINS(E, lane, { psi[i] = __float_as_uint(ph[i]) + __float_as_uint(own[i]); })
+        } else {
+            PV_FOR_BINS(E, lane, { psi[i] = (unsigned)M[i]; })
+        }
+        PV_FOR_BINS(E, lane, {
+            float sn, cs;
+            sincos_rev(turns_rev(psi[i]), &sn, &cs);
+            float2 y = make_float2(mag[i] * cs, mag[i] * sn);
+            if (k == 0 || k == L) y.y = 0.0f;
             Yr[i] = y;
         })
     } else if constexpr (MODE != 1) {

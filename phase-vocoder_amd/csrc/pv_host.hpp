@@ -30,11 +30,13 @@ pv_status fail(pv_status s, const std::string& msg);
     } while (0)
 
 // kernel ids of the per-launch profile and their names (pv_profile_read), index for index
-enum { KA, KRS, KC, KS, KSEAM, KCA, KRT, KF, KSL, KENV, KSF, KRES, KRTR, KSW, KON, KPK, KRST, KSR, kNumKernels };
+enum { KA, KRS, KC, KS, KSEAM, KCA, KRT, KF, KSL, KENV, KSF, KRES, KRTR, KSW, KON, KPK, KRST, KSR, KMS, KMC, KSM,
+       kNumKernels };
 inline constexpr const char* kKernelNames[] = {"analysis", "runsum", "carry", "synthesis", "seam",
                                                "compat_analysis", "rt", "fused", "synthesis_locked",
                                                "envelope", "synthesis_formant", "resample", "rt_resample",
-                                               "synthesis_warp", "onset", "pick", "reset", "synthesis_reset"};
+                                               "synthesis_warp", "onset", "pick", "reset", "synthesis_reset",
+                                               "map_sum", "map_carry", "synthesis_map"};
 static_assert(sizeof(kKernelNames) / sizeof(kKernelNames[0]) == kNumKernels, "one name per kernel id");
 
 // Move-only owner of one hipMalloc (Pinned: hipHostMalloc, device-mapped) allocation.  Converts
@@ -145,6 +147,12 @@ struct pv_handle {
     pvhost::DevBuf<float> d_tr_theta;
     pvhost::DevBuf<int> d_tr_prr;
     std::mutex tr_mu;
+    // pv_timemap_set: the time map {i_u, a_u} of pv_timemap_process (max_frames entries), its
+    // length (0: no map) and highest row index, and the integer phase scan's run sums and
+    // carries, [max_channels][max_runs][bins_pad] each (allocated by the first set, zeroed)
+    int map_n = 0, map_imax = 0;
+    pvhost::DevBuf<pv::MapEntry> d_map;
+    pvhost::DevBuf<unsigned> d_map_sum, d_map_carry;
     float scale = 1.0f, rho = 1.0f, inv_q = 1.0f;
     unsigned long long p_mod = 0, q = 1;
     int q_pow2 = 1;
@@ -288,6 +296,13 @@ pv_status do_fused(pv_handle* h, const float* x, long long ldx, long long n, int
 // pv_process after its checks (the caller holds the device guard and the profile call)
 pv_status process_impl(pv_handle* h, const float* x, long long ldx, long long n_samples, int channels, int frames,
                        pv_float2* spec, long long ld_spec, float* out, long long ldo, hipStream_t s);
+// the parts of do_resynthesis and process_impl that pv_timemap_process shares: the synthesis
+// arguments every mode starts from, the seam launch, the handle's own rows of a spec = NULL call
+pv::SynParams syn_params(const pv_handle* h, const pv_float2* spec, long long ld_spec, int frames, float* out,
+                         long long ldo, long long olen);
+pv_status do_seam(pv_handle* h, int C, int frames, const float* ola_in, long long ld_ola, float* out, long long ldo,
+                  long long olen, hipStream_t s);
+pv_status own_spectrum(pv_handle* h, const char* fn, hipStream_t s, pv_float2** spec, long long* ld_spec);
 // own_rows: allocate the handle's envelope rows (a harmoniser's voices k > 0 read voice 0's)
 pv_status set_formant(pv_handle* h, int order, bool own_rows);
 

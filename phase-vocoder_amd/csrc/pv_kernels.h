@@ -134,6 +134,41 @@ inline void set_reset_args(SynParams* p, const ResetArgs& a) {
     p->src_first = a.prev_reset_run;
 }
 
+// The time-map stretch (pv_timemap.hip).  Output frame u is built at analysis
+// position i_u + a_u: map[u] = {i_u, a_u} (pv_timemap_split), one map for all channels.
+struct MapEntry {
+    int idx;
+    float frac;
+};
+// The map modes' view of SynParams (no pitch map, no envelope; `frames`, F, nruns count output
+// frames; `carry` is k_map_carry's, Phi at every run's first frame): the map and the number of
+// analysed rows, every idx <= aframes - 1 (checked by the host)
+struct MapArgs {
+    const MapEntry* map;
+    int aframes;
+};
+__host__ __device__ inline MapArgs map_args(const SynParams& p) {
+    return MapArgs{reinterpret_cast<const MapEntry*>(p.src_first), p.env_stride};
+}
+inline void set_map_args(SynParams* p, const MapArgs& a) {
+    p->src_first = reinterpret_cast<const int*>(a.map);
+    p->env_stride = a.aframes;
+}
+// k_map_sum: sum[(c * nruns + r) * bins_pad + k] = the sum over run r's output frames u of
+// Delta(i_u)[k] = P(i_u + 1)[k] - P(i_u)[k] (0 for i_u = aframes - 1), modulo 2^32;
+// k_map_carry: carry[(c * nruns + r) * bins_pad + k] = P(i_0)[k] + the sums of the runs before r
+struct MapScanParams {
+    const float2* spec;
+    long long ld_spec;
+    int spec_stride, aframes;
+    int frames, F, nruns;              // output frames (the map's length), per run, runs
+    int L, bins_pad;
+    int packed;                        // PV_SPEC_PACKED rows
+    const MapEntry* map;
+    unsigned* sum;
+    unsigned* carry;
+};
+
 // transient detector and reset offsets (pv_transient.hip)
 // k_onset: dst[c * ld_dst + t] = {rise, tot} of frame t: rise = sum over bins 0 .. L of
 // max(0, mag_t[k] - mag_{t-1}[k]) (mag_{-1} = 0), tot = sum of mag_t[k]; fp32, the kernel's order
@@ -331,6 +366,14 @@ hipError_t launch_onset(int L, int channels, const OnsetParams& p, hipStream_t s
 hipError_t launch_pick(int channels, const PickParams& p, hipStream_t s);
 hipError_t launch_reset(int L, int channels, const ResetParams& p, hipStream_t s);
 hipError_t launch_synthesis_reset(int L, int lock, int channels, const SynParams& p, hipStream_t s);
+// The time-map stretch (pv_timemap.hip; pv_timemap_process): launch_map_sum, launch_map_carry,
+// then launch_synthesis's mode 0, or launch_synthesis_locked with lock != 0, at out hop = hop with
+// the map's phases and magnitudes (set_map_args; ek, jk_mod, k_lane and src_hi are not used);
+// register overlap-add at hop 128 / 256 / 512, the LDS ring otherwise; same tails for
+// launch_seam.  L <= 1024.
+hipError_t launch_map_sum(int channels, const MapScanParams& p, hipStream_t s);
+hipError_t launch_map_carry(int channels, const MapScanParams& p, hipStream_t s);
+hipError_t launch_synthesis_map(int L, int lock, int channels, const SynParams& p, hipStream_t s);
 // the synthesis kernel for this geometry can take SynParams.k_lane (register overlap-add,
 // power-of-two q, STANDARD)
 bool synthesis_lane_kernel(int L, int mode, int hs, bool q_pow2, unsigned long long q);

@@ -12,6 +12,9 @@ constexpr int kModeLocked = 6;
 // ... and of the stretch with the transient phase reset (pv_transient.hpp), unlocked and locked
 constexpr int kModeReset = 10;
 constexpr int kModeLockedReset = 11;
+// ... and of the time-map stretch (pv_timemap.hpp), unlocked and locked
+constexpr int kModeMap = 12;
+constexpr int kModeLockedMap = 13;
 
 // A wave holds the frame: bin k = lane + 64 i in register slot i (i < E), bin L = 64 E in slot
 // E of lane 0.  Slot E of the other lanes stands for the bins past L, which do not exist: they

@@ -2,7 +2,8 @@
 // around syn_run, pv_syn_run.hpp) that every synthesis mode instantiates, and its launch
 // geometry.  The translation units pick their modes: pv_kernels.hip MODE 0..3 (with the
 // per-lane-constant and partial-row variants), pv_locked.hip kModeLocked, pv_formant.hip
-// kModeFormant, pv_warp.hip kModeWarp / kModeLockedWarp.
+// kModeFormant, pv_warp.hip kModeWarp / kModeLockedWarp, pv_transient.hip kModeReset /
+// kModeLockedReset, pv_timemap.hip kModeMap / kModeLockedMap.
 #pragma once
 #include "pv_syn_run.hpp"
 
@@ -25,6 +26,11 @@ namespace pv {
 //         (pv_transient.hpp): one more additive phase offset per bin, Theta, kept in the wave's
 //         registers — from the last flagged run before this one and replaced at the run's own
 //         flagged frames (reset_args, pv_kernels.h).
+// kModeMap / kModeLockedMap: the time-map stretch (pv_timemap.hpp; out hop = hop): `frames` output
+//         frames, each from the two analysis rows around its map position (map_args,
+//         pv_kernels.h); the running phase Phi, a 32-bit fraction of a turn, takes the place of
+//         the unwrap count in the wave's registers (its carry is k_map_carry's).  Launched with
+//         q = 1 (QPOW2): there is no output-phase denominator.
 // Overlap-add: a position is final once the frame that starts after it has been added;
 // final samples are stored straight to `out`.
 //   DT > 0 (out hop = 128 DT, L <= 1024): in registers.  After the inverse FFT's last pass
@@ -81,7 +87,7 @@ __global__ __launch_bounds__(256, (L <= 256) ? 4 : (L == 512) ? (MODE >= kModeLo
     for (int i = tid; i < L; i += 256) { twl[i] = p.tw[i]; twsl[i] = p.tws[i]; }
     if (!GREG)
         for (int i = tid; i < N; i += 256) gainl[i] = p.gain[i];
-    if (MODE != 1) {
+    if (MODE != 1 && !mode_is_map(MODE)) {  // (the map modes read no unwrap table)
         for (int i = tid; i < B; i += 256) {
             ekl[i] = p.ek[i];
             // RACC: (p j_k mod q) / q as a float (exact: q <= 4096)
@@ -142,6 +148,12 @@ __global__ __launch_bounds__(256, (L <= 256) ? 4 : (L == 512) ? (MODE >= kModeLo
         const ResetRun<E> rs{th, ra.flags + (long long)c * ra.ld_flags + t0};
         syn_run<L, MODE, DT, QPOW2, LANEK, NR, ResetRun<E>>(
             p, SynCarve{twl, twsl, tiles, rings, gainl, ekl, jkl, srcl}, tw0, lane, w, c, t0, nfr, M, phprev, acc, rs);
+    } else if constexpr (mode_is_map(MODE)) {
+        // M holds Phi at the run's first frame: the carry k_map_carry wrote (loaded above)
+        const MapArgs ma = map_args(p);
+        syn_run<L, MODE, DT, QPOW2, LANEK, NR, NoResetRun, MapRun>(
+            p, SynCarve{twl, twsl, tiles, rings, gainl, ekl, jkl, srcl}, tw0, lane, w, c, t0, nfr, M, phprev, acc,
+            NoResetRun{}, MapRun{ma.map + t0, ma.aframes});
     } else
     syn_run<L, MODE, DT, QPOW2, LANEK, NR>(
         p, SynCarve{twl, twsl, tiles, rings, gainl, ekl, jkl, srcl}, tw0, lane, w, c, t0, nfr, M, phprev, acc);

@@ -230,7 +230,8 @@ struct SynTraits {
     static constexpr bool GREG = syn_gains_in_regs(L, DT);
     // revolution accumulator (synth_frame RACC; measured: synthesis -2.5 %); the host takes
     // the QPOW2 kernels only for q <= 4096
-    static constexpr bool RACC = QPOW2 && MODE != 1;
+    // (the map modes carry an integer phase in M, not the unwrap count)
+    static constexpr bool RACC = QPOW2 && MODE != 1 && !mode_is_map(MODE);
 };
 
 // The frame loop of one wave's run: frames t0 .. t0 + F - 1 of channel c (frames >= nfr are
@@ -247,11 +248,15 @@ struct SynTraits {
 // (k_std_analysis NA): they stay zero in the registers, no load, no stale bytes read.
 // RS: the reset modes' state (ResetRun, pv_transient.hpp): the wave's Theta registers and the
 // run's flag bytes, read 64 frames at a time as one ballot (once per run for F <= 64).
-template <int L, int MODE, int DT, bool QPOW2, bool LANEK = false, int NR = Geo<L>::E, typename RS = NoResetRun>
+// MP: the map modes' state (MapRun, pv_timemap.hpp): the run's map entries; M holds Phi, the
+// running phase as a 32-bit fraction of a turn (the caller loads the run's carry into it).
+template <int L, int MODE, int DT, bool QPOW2, bool LANEK = false, int NR = Geo<L>::E, typename RS = NoResetRun,
+          typename MP = NoMapRun>
 __device__ __forceinline__ void syn_run(const SynParams& p, const SynCarve& sc, const float2 (&tw0)[Geo<L>::E],
                                         int lane, int w, int c, int t0, int nfr,
                                         int (&M)[Geo<L>::E + 1], float (&phprev)[Geo<L>::E + 1],
-                                        float2 (&acc)[SynTraits<L, MODE, DT, QPOW2>::NS], const RS& rs = RS{}) {
+                                        float2 (&acc)[SynTraits<L, MODE, DT, QPOW2>::NS], const RS& rs = RS{},
+                                        const MP& mp = MP{}) {
     using G_ = Geo<L>;
     using T_ = SynTraits<L, MODE, DT, QPOW2>;
     constexpr bool ROLA = T_::ROLA;
@@ -315,6 +320,7 @@ __device__ __forceinline__ void syn_run(const SynParams& p, const SynCarve& sc, 
     }
     const unsigned q32 = (unsigned)p.q;  // <= 2^24 (QPOW2) or <= 32768
     static_assert(RS::ON == mode_is_reset(MODE), "the reset state goes with the reset modes");
+    static_assert(MP::ON == mode_is_map(MODE), "the map state goes with the map modes");
     unsigned long long flagw = 0;  // reset modes: the flags of frames 64 (u / 64) .. + 63 of the run
     (void)flagw;
     // (env: the frame's log envelope row, formant and warp modes; NoEnv otherwise)
@@ -392,7 +398,92 @@ __device__ __forceinline__ void syn_run(const SynParams& p, const SynCarve& sc, 
     // (the formant synthesis reads its envelope rows with plain loads: no self-tracked prefetch)
     constexpr bool FASTOK = ROLA && L == 512 && !FORMANT;
     const bool fast = FASTOK && nfr == p.F && p.out_aligned && obase + (long long)p.F * hs <= p.out_len;
-    if (FASTOK && fast) {
+    if constexpr (MP::ON) {
+        // The map modes: frame u reads rows i_u and i_u + 1 (wave-uniform map
+        // entry, scalar reads; plain loads), lerps the magnitudes, and Phi advances by the rows'
+        // phase step after the frame.  i_u = aframes - 1: row `aframes` is not loaded (magnitude
+        // 0, step 0).  The host has checked every index.  L <= 512: the rows are loaded one frame
+        // ahead; L = 1024: at the frame's start (two more rows live across the frame do not fit
+        // 256 VGPRs, and with AGPRs the kernel would hold 1 wave/SIMD where its LDS allows 2).
+        constexpr bool AHEAD = L <= 512;
+        const int alast = mp.aframes - 1;
+        const bool fast_st = ROLA && p.out_aligned && obase + (long long)p.F * hs <= p.out_len;
+        (void)fast_st;
+        // DT = 0, as in the loop of the other modes below (whose code stays as it is: its
+        // instructions are the parent's, scripts/asm_diff.py): overlap-add the frame (time samples
+        // in the tile) into the ring, lane-distinct positions
+        auto ola_ring = [&](int u) {
+            constexpr int ROT = (MODE == 1) ? N / 2 : 0;
+            const float* ty = reinterpret_cast<const float*>(tile) + 2 * G_::pad(lane >> 1) + (lane & 1);
+            const int rbase = u * hs + lane;
+#pragma unroll
+            for (int i = 0; i < SPW; ++i) {
+                const int n = lane + 64 * i;
+                const int cc = ((64 * i + ROT) & (N - 1)) >> 1;
+                const float yv = ty[2 * G_::padc(cc)];
+                const int pos = (rbase + 64 * i) & (N - 1);
+                ring[pos] = __builtin_fmaf(yv, gainl[n], ring[pos]);
+            }
+            wave_lds_sync();
+        };
+        // DT = 0 flush of frame u: positions [u*hs, (u+1)*hs) are final for this run
+        auto flush_ring = [&](int u) {
+            for (int j = lane; j < hs; j += 64) {
+                const int pl = u * hs + j;
+                const int slot = pl & (N - 1);
+                const float v = ring[slot];
+                ring[slot] = 0.0f;
+                if (obase + pl < p.out_len) outc[obase + pl] = v;
+            }
+            wave_lds_sync();
+        };
+        float2 ra[E + 1], rb[E + 1];  // rows i_u, i_u + 1 of the next frame
+        int iu = 0;
+        float au = 0.0f;
+        auto load_rows = [&](int u) {
+            iu = __builtin_amdgcn_readfirstlane(mp.map[u].idx);
+            au = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(mp.map[u].frac)));
+            const float2* r0 = specc + (long long)iu * p.spec_stride;
+            const float2* r1 = r0 + (iu < alast ? p.spec_stride : 0);  // (the last row twice: one path)
+            PV_FOR_BINS(E, lane, {
+                if (i < E || !packed) { ra[i] = r0[k]; rb[i] = r1[k]; }
+            })
+        };
+        if (AHEAD && nfr > 0) load_rows(0);
+        for (int u = 0; u < p.F; ++u) {
+            if (u < nfr) {
+                if (!AHEAD) load_rows(u);
+                unpack(ra);
+                unpack(rb);
+                const bool two = iu < alast;  // wave-uniform
+                const float a = au;
+                float2 sv[E + 1];
+                unsigned dl[E + 1];
+                PV_FOR_BINS(E, lane, {
+                    const unsigned p0 = phase_turns(ra[i].y);
+                    const float m1 = two ? rb[i].x : 0.0f;
+                    sv[i] = make_float2(__builtin_fmaf(a, m1 - ra[i].x, ra[i].x), __uint_as_float(p0));
+                    dl[i] = two ? phase_turns(rb[i].y) - p0 : 0u;
+                })
+                if (AHEAD && u + 1 < nfr) load_rows(u + 1);
+                float2 z[E];
+                synth(u, t0 + u, sv, z, NoHook{}, ev);
+                PV_FOR_BINS(E, lane, { M[i] = (int)((unsigned)M[i] + dl[i]); })
+                if constexpr (ROLA) {
+                    ola_regs(z);
+                    __builtin_amdgcn_s_waitcnt(kVmcnt0);  // (the next rows, before the frame's stores)
+                } else {
+                    ola_ring(u);
+                }
+            }
+            if constexpr (ROLA) {
+                if (fast_st) flush_regs(u, std::true_type{});
+                else flush_regs(u, std::false_type{});
+            } else {
+                flush_ring(u);
+            }
+        }
+    } else if (FASTOK && fast) {
         // every store of the run is in bounds: trip u = [load row u+1] [frame u] [D stores]
         // [vmcnt(D): row u+1 landed, the stores may still be in flight].  Two row buffers
         // alternate (F is even), so no register copies carry a row across trips.

@@ -212,6 +212,19 @@ void warp_map(int bins, int hop, int out_hop, std::vector<int>& idx, std::vector
     }
 }
 
+// the time map's split (pv_timemap_split): i = floor(pos), a = fp32(pos - i)
+// (the difference is exact in fp64; a may round up to 1)
+bool timemap_split(const double* pos, int n, int* idx, float* frac) {
+    for (int u = 0; u < n; ++u) {
+        const double x = pos[u];
+        if (!std::isfinite(x) || x < 0.0 || x >= 1073741824.0) return false;
+        const double fl = std::floor(x);
+        idx[u] = (int)fl;
+        frac[u] = (float)(x - fl);
+    }
+    return true;
+}
+
 EnvOverrides read_env_overrides() {
     EnvOverrides e;
     // the single-launch and REF_COMPAT overrides (pv.h)

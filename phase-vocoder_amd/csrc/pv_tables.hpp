@@ -62,6 +62,10 @@ void pitch_map(int bins, bool pitch, float scale, PitchMap& m);
 // to {L, 0}.  Not part of the exported table blob.
 void warp_map(int bins, int hop, int out_hop, std::vector<int>& idx, std::vector<float>& frac);
 
+// ---- time map (pv_timemap_split): pos[u] -> {floor, fp32 fraction}; false (idx / frac then
+// partly written) on a position that is not finite, negative or >= 2^30
+bool timemap_split(const double* pos, int n, int* idx, float* frac);
+
 // ---- environment overrides (pv.h lists them), read once per pv_create
 struct EnvOverrides {
     int compat_ana_frames = 4;                 // PV_COMPAT_ANA_FRAMES in [1, 256]

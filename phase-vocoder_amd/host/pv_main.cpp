@@ -29,6 +29,12 @@
 //                                        it): --mode std with effect t and --batched or
 //                                        --pitch-resample; composes with --phase-lock; not with
 //                                        --pitch-formant or --rt
+//     --rate R                           time-map stretch at the constant playback rate R > 0
+//                                        (pv_timemap_process; positions 0, R, 2R, .. up to the last
+//                                        frame: R < 1 stretches, any real value): --mode std with
+//                                        effect t at scale 1 (--scale is ignored), every channel in
+//                                        one call; composes with --phase-lock; not with --rt,
+//                                        --transients or --pitch-resample
 //     --single-arg                       PhaseVocoder(N): periodic Hann, hop N/2 (phaseVocoder.h:46-78)
 //     --nan-faithful                     atanf(0/0) = NaN phases as the reference (kernel.cu:101-109)
 //     --timer                            print CudaPhase::timer() per call (main.cpp:238-241, 275-278)
@@ -97,6 +103,7 @@ int main(int argc, char** argv) {
     bool transients = false;
     float transient_thr = 0.0f;  // 0: PV_TRANSIENT_DEFAULT_THRESHOLD
     int pitch_resample = -1;  // --pitch-resample: quality preset (0 fast, 1 best)
+    double rate = 0.0;        // --rate: the time map's playback rate (0: no map)
     double ana_ms = 0.0, syn_ms = 0.0;
     pv_mode mode = PV_MODE_REF_COMPAT;
     std::vector<std::string> pos;
@@ -124,6 +131,13 @@ int main(int argc, char** argv) {
                     transient_thr = v;
                     ++i;
                 }
+            }
+        }
+        else if (a == "--rate" && i + 1 < argc) {
+            rate = std::atof(argv[++i]);
+            if (!(rate > 0.0) || !(rate < 1e6)) {
+                std::fprintf(stderr, "err: --rate R, R > 0\n");
+                return 1;
             }
         }
         else if (a == "--pitch-formant" && i + 1 < argc) pitch_formant = std::atoi(argv[++i]);
@@ -158,10 +172,24 @@ int main(int argc, char** argv) {
         scale = 1.0f;
         mode = PV_MODE_REF_COMPAT;
     }
+    if (rate > 0.0) {
+        if (rt || transients || pitch_resample >= 0 || pitch_formant != 0 || single_arg || mode != PV_MODE_STANDARD ||
+            effect != TIME_SHIFT) {
+            std::fprintf(stderr, "err: --rate needs --mode std with effect t (not --rt, --transients, --pitch-resample, "
+                         "--single-arg)\n");
+            return 1;
+        }
+        scale = 1.0f;  // the map replaces the scale
+    }
     const int hop = N / hopdiv;
     const int frames = pv_frame_count(numSamples, hop);
     const int padN = numSamples + 2 * N;  // frames near the end read zeros (deviation 1)
-    const int cap = frames + numSamples / std::max(1, (int)(scale * hop)) + 2;
+    // the time map: positions 0, rate, 2 rate, .. <= frames - 1
+    std::vector<double> map_pos;
+    if (rate > 0.0)
+        for (long long u = 0; frames > 0 && (double)u * rate <= (double)(frames - 1) + 1e-9 && u < (1LL << 24); ++u)
+            map_pos.push_back(std::min((double)u * rate, (double)(frames - 1)));
+    const int cap = std::max(frames + numSamples / std::max(1, (int)(scale * hop)) + 2, (int)map_pos.size());
     std::unique_ptr<PhaseVocoder> owner(
         single_arg ? new PhaseVocoder(N, numChannels > 0 ? numChannels : 1, cap)  // phaseVocoder.h:46
                    : new PhaseVocoder(N, effect, scale, hopdiv, mode, numChannels > 0 ? numChannels : 1, cap));
@@ -221,8 +249,14 @@ int main(int argc, char** argv) {
             return 1;
         }
     }
-    // (the resampled stretch has the input's duration)
-    const int outLen = pitch_resample >= 0 ? numSamples : (int)(phase.timeScale * numSamples);
+    if (rate > 0.0 && !map_pos.empty() &&
+        pv_timemap_set(phase.handle, map_pos.data(), (int)map_pos.size()) != PV_OK) {
+        std::fprintf(stderr, "err: --rate: %s\n", pv_last_error());
+        return 1;
+    }
+    // (the resampled stretch has the input's duration; the map's output, its frames' span)
+    const int outLen = rate > 0.0 ? (int)pv_output_length(phase.handle, (int)map_pos.size())
+                       : pitch_resample >= 0 ? numSamples : (int)(phase.timeScale * numSamples);
     std::vector<std::vector<float>> outFile(2, std::vector<float>(outLen > 0 ? outLen : 0, 0.f));
 
     float* d_input = nullptr;  // [channel][padN], zero padded
@@ -268,6 +302,26 @@ int main(int argc, char** argv) {
             for (long long i = 0; i < n_emit; ++i) outFile[c][i] = h[i];
             if (c == 0) {
                 emitted.assign(h.begin(), h.begin() + n_emit);
+                if (numChannels == 1) outFile[1] = outFile[0];
+            }
+        }
+        HIPCHECK(hipFree(d_out));
+    } else if (rate > 0.0) {
+        const long long olen = outLen;
+        float* d_out = nullptr;
+        HIPCHECK(hipMalloc((void**)&d_out, sizeof(float) * (size_t)std::max(olen, 1LL) * std::max(numChannels, 1)));
+        if (olen > 0)
+            PhaseVocoder::checkCUDAErrori(pv_timemap_process(phase.handle, d_input, padN, numSamples, numChannels,
+                                                             frames, nullptr, 0, d_out, olen, nullptr),
+                                          "pv_timemap_process", __LINE__);
+        HIPCHECK(hipDeviceSynchronize());
+        std::vector<float> h((size_t)std::max(olen, 1LL));
+        // channel 0 to L, channel 1 (channel 0 of a mono file) to R
+        for (int c = 0; c < std::min(numChannels, 2) && olen > 0; ++c) {
+            HIPCHECK(hipMemcpy(h.data(), d_out + (size_t)c * olen, sizeof(float) * olen, hipMemcpyDeviceToHost));
+            for (long long i = 0; i < olen; ++i) outFile[c][i] = h[i];
+            if (c == 0) {
+                emitted.assign(h.begin(), h.begin() + olen);
                 if (numChannels == 1) outFile[1] = outFile[0];
             }
         }

@@ -2,10 +2,10 @@
 (the MI355X HIP phase-vocoder hot path).  See DESIGN.md and include/pv.h."""
 from ._lib import PVError, frame_count, lib  # noqa: F401
 from .vocoder import (PITCH_SHIFT, REF_COMPAT, STANDARD, TIME_SHIFT,  # noqa: F401
-                      PhaseVocoder)
+                      PhaseVocoder, rate_map, timemap_split)
 from .realtime import RealTimeVocoder  # noqa: F401
 from .harmonizer import Harmonizer  # noqa: F401
 from .resample import Resampler  # noqa: F401
 
 __all__ = ["PhaseVocoder", "PVError", "TIME_SHIFT", "PITCH_SHIFT", "REF_COMPAT", "STANDARD", "RealTimeVocoder", "Harmonizer",
-           "Resampler", "frame_count", "lib"]
+           "Resampler", "frame_count", "lib", "rate_map", "timemap_split"]

@@ -222,6 +222,14 @@ def lib():
     L.pv_transient_get_flags.restype = i
     L.pv_onset_strength.argtypes = [vp, vp, ll, i, i, vp, ll, vp]
     L.pv_onset_strength.restype = i
+    L.pv_timemap_split.argtypes = [vp, i, vp, vp]
+    L.pv_timemap_split.restype = i
+    L.pv_timemap_set.argtypes = [vp, vp, i]
+    L.pv_timemap_set.restype = i
+    L.pv_timemap_frames.argtypes = [vp]
+    L.pv_timemap_frames.restype = i
+    L.pv_timemap_process.argtypes = [vp, vp, ll, ll, i, i, vp, ll, vp, ll, vp]
+    L.pv_timemap_process.restype = i
     _lib = L
     return L
 

@@ -36,6 +36,24 @@ def _ptr(t) -> int:
     return 0 if t is None else int(t.data_ptr())
 
 
+def rate_map(frames: int, rate: float) -> np.ndarray:
+    """The time map of a constant playback rate over `frames` analysed frames: positions 0, rate,
+    2 rate, .. up to frames - 1 (float64), for `PhaseVocoder.set_time_map`.  rate < 1 stretches."""
+    return np.arange(0, frames - 1 + 1e-9, rate).astype(np.float64)
+
+
+def timemap_split(pos):
+    """pv_timemap_split (pure host, no GPU): positions -> (floor as int32, fraction as float32).
+    Raises PVError on a position that is not finite, negative or >= 2^30."""
+    pos = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1)
+    idx = np.empty(pos.size, dtype=np.int32)
+    frac = np.empty(pos.size, dtype=np.float32)
+    vp = ctypes.c_void_p
+    _lib.check(_lib.lib().pv_timemap_split(pos.ctypes.data_as(vp), int(pos.size), idx.ctypes.data_as(vp),
+                                           frac.ctypes.data_as(vp)), "pv_timemap_split")
+    return idx, frac
+
+
 class PhaseVocoder:
     """`class PhaseVocoder` (src/phaseVocoder.h:9-139) on the MI355X HIP path."""
 
@@ -367,6 +385,44 @@ class PhaseVocoder:
                                       _ptr(spec) if spec is not None else None,
                                       spec.stride(0) // 2 if spec is not None else 0, _ptr(out),
                                       out.stride(0), self._stream(stream)), "pv_process")
+        return out, spec
+
+    # -------------------------------------------------------------- time-map stretch
+    def set_time_map(self, positions):
+        """pv_timemap_set: output frame u of `time_map_process` is built at the fractional
+        analysis position positions[u] (frames, float64; finite, >= 0; need not be monotonic:
+        a freeze, a scrub and a reverse are maps; see `rate_map`).  One map for all channels;
+        at most max_frames entries.  STANDARD time-stretch handles at scale 1.  None clears it."""
+        if positions is None:
+            self._call(self._L.pv_timemap_set(self._h, None, 0), "pv_timemap_set")
+            return
+        pos = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1)
+        self._call(self._L.pv_timemap_set(self._h, pos.ctypes.data_as(ctypes.c_void_p), int(pos.size)),
+                   "pv_timemap_set")
+
+    @property
+    def time_map_frames(self) -> int:
+        return int(self._L.pv_timemap_frames(self._h))
+
+    def time_map_process(self, x, frames: int | None = None, n_samples: int | None = None, spec=None,
+                         out=None, stream=None, spectrum: bool = True):
+        """pv_timemap_process: analysis of x's `frames` frames, then the handle's time map ->
+        (out [C, output_length(time_map_frames)], spec), as `process` does (spectrum=False: the
+        handle's own rows)."""
+        x = self._as2d(x)
+        C, n = x.shape
+        n_samples = n if n_samples is None else n_samples
+        frames = self.num_frames(n_samples) if frames is None else frames
+        if not spectrum and spec is not None:
+            raise ValueError("spectrum=False with a spec buffer")
+        if spectrum and spec is None:
+            spec = self.alloc_spec(C, frames)
+        if out is None:
+            out = self.alloc_out(C, self.time_map_frames)
+        self._call(self._L.pv_timemap_process(self._h, _ptr(x), x.stride(0), n_samples, C, frames,
+                                              _ptr(spec) if spec is not None else None,
+                                              spec.stride(0) // 2 if spec is not None else 0, _ptr(out),
+                                              out.stride(0), self._stream(stream)), "pv_timemap_process")
         return out, spec
 
     # -------------------------------------------------------------- pitch shift by resampling
