@@ -79,7 +79,10 @@ extern "C" {
                                 pv_resample_length, pv_pitch_reserve / pv_pitch_process /
                                 pv_pitch_output_length, pv_rt_set_phase_lock /
                                 pv_rt_get_phase_lock, pv_rt_pitch_reserve / pv_rt_pitch_latency /
-                                pv_rt_pitch_push, pv_pitch_set_formant / pv_pitch_get_formant) */
+                                pv_rt_pitch_push, pv_pitch_set_formant / pv_pitch_get_formant,
+                                pv_varresampler_* / pv_varresample / pv_varresample_steps /
+                                pv_varresample_length, pv_pitchmap_plan / pv_pitchmap_set /
+                                pv_pitchmap_output_length / pv_pitchmap_process) */
 
 typedef struct pv_handle pv_handle;
 
@@ -507,6 +510,84 @@ int pv_timemap_frames(const pv_handle* h);
 pv_status pv_timemap_process(pv_handle* h, const float* x, long long ldx, long long n_samples, int channels,
                              int frames, pv_float2* spec, long long ld_spec, float* out, long long ldo,
                              void* stream);
+
+/* ---------------------------------------------------------------- variable-rate resampler
+ * Band-limited resampling by a ratio that changes along the signal, and the pitch map built on
+ * it.  The output is cut into blocks of B samples (`block`, fixed at creation,
+ * 16 <= B <= 4096).  The map is a start position and one step per block, 64-bit integers in
+ * units of 2^-32 input samples:
+ *   positions T_0 = start >= 0, T_{b+1} = T_b + B d_b, all <= 2^62.  Output m = b B + j (j < B)
+ *             reads the input at t_m = T_b + j d_b: i_m = t_m >> 32, fq_m = t_m & 0xffffffff,
+ *             exact integers.  2^30 <= d_b <= 2^34 (ratio 1/4 .. 4): constant within a block,
+ *             free to jump between blocks.  pv_varresample_steps: d = llrint(ratio 2^32).
+ *   filter    per block, with pv_resampler_create's presets {Z, rolloff, beta}: Sq_b = the
+ *             largest even 32-bit integer <= rolloff min(1, 2^32 / d_b) 2^32 (fp64),
+ *             s_b = Sq_b / 2^32, W_b = ceil(Z / s_b), and h_b the resampler's h with s = s_b.
+ *   output    y[m] = sum_{j = -W_b+1}^{W_b} x[i_m + j] h_b(j - fq_m / 2^32); x reads as 0
+ *             outside [0, n_in) (masked: what lies there, a NaN included, is never loaded)
+ * Every step 2^32 and a start without a fraction: the rows shifted by start >> 32, no filter.
+ * No coefficient table can exist; the kernel computes every tap's coefficient in fp32 (the sine
+ * from an exact integer fraction of a turn) and accumulates in fp32 in its own order: tolerance
+ * bound like pv_resample, no bit-exact contract.
+ * pv_varresampler_create allocates the device records of max_blocks blocks, zeroed (max_blocks
+ *   * block < 2^31); pv_varresampler_set_map validates the map, builds the per-block records and
+ *   the per-tile input spans on the host and uploads them between two synchronisations: setup
+ *   calls, not capturable.  pv_varresample_length: nblocks * block, 0 without a map or for NULL.
+ * pv_varresample: y[c*ldy + m], m < n_out <= pv_varresample_length, from x[c*ldx + i], i < n_in;
+ *   device pointers on the resampler's device.  One launch (in a handle's profile:
+ *   var_resample), no allocation, no synchronisation: capturable.  channels or n_out 0: nothing
+ *   is done (PV_OK).
+ * PV_ERR_ARG, each with a pv_last_error text: a NULL object or argument; quality other than 0, 1,
+ *   block outside [16, 4096], max_blocks < 1; nblocks outside [1, max_blocks]; a step out of
+ *   range; a negative start or positions past 2^62; pv_varresample before a map; n_out > length;
+ *   x and y overlapping; ldx < n_in or ldy < n_out with more than one channel; a ratio that is
+ *   not finite or outside [1/4, 4], or n <= 0. */
+typedef struct pv_varresampler pv_varresampler;
+pv_status pv_varresampler_create(int quality, int block, int max_blocks, int device, pv_varresampler** out);
+void pv_varresampler_destroy(pv_varresampler* vr);
+pv_status pv_varresample_steps(const double* ratio, int n, long long* step);
+pv_status pv_varresampler_set_map(pv_varresampler* vr, long long start, const long long* step, int nblocks);
+long long pv_varresample_length(const pv_varresampler* vr);
+pv_status pv_varresample(pv_varresampler* vr, const float* x, long long ldx, long long n_in, int channels,
+                         float* y, long long ldy, long long n_out, void* stream);
+
+/* Pitch map: a time-varying pitch ratio beside a time-varying tempo, as "time map, then
+ * variable-rate resampling" (pv_pitch_process is "stretch, then pv_resample").  On the handles
+ * pv_timemap_set accepts.  Per final output frame u < n the caller gives pos[u], the analysis
+ * position that frame sounds at (the tempo curve: pv_timemap_set's map when the pitch is left
+ * alone), and ratio[u], the pitch ratio there.  The output keeps pv_output_length(h, n) samples.
+ *   Plan (pv_pitchmap_plan: pure host, no handle, no GPU; integers and fp64).  With N = n_samps,
+ *     L = n hop + N - hop: nb = ceil(L / hop) blocks of hop samples with d_b = llrint(ratio[b]
+ *     2^32), the last ratio repeated over the blocks b >= n.  Sigma_0 = 0, Sigma_{b+1} = Sigma_b
+ *     + hop d_b: the resampler reads the stretched signal at Sigma.  The stretch has n_s =
+ *     max(1, ceil(Sigma_n / (hop 2^32))) frames; frame v, at t = v hop 2^32, lies in the block
+ *     b <= n - 1 with Sigma_b <= t < Sigma_{b+1}, w = (t - Sigma_b) / (Sigma_{b+1} - Sigma_b) (one
+ *     fp64 division of exact integers), pos_s[v] = pos[b] + w (pos[min(b+1, n-1)] - pos[b]).
+ *     Writes pos_s[*n_s] (at most 4 n + 1) and step[*n_steps] (nb).  PV_ERR_ARG on NULL, n < 1,
+ *     n hop >= 2^28, hop < 1 or > n_samps, a position pv_timemap_split refuses, a ratio
+ *     pv_varresample_steps refuses, or a capacity too small.
+ *   pv_pitchmap_set plans, installs pos_s as pv_timemap_set does (pv_timemap_frames then reads
+ *     n_s; n or n_s > max_frames: PV_ERR_ARG), and creates or re-maps the handle's variable-rate
+ *     resampler (blocks of hop samples, 16 <= hop <= 4096).  A setup call.  Its first call
+ *     allocates the scratch rows, max_channels x pv_output_length(h, max_frames) floats (those
+ *     of pv_pitch_reserve); on PV_ERR_NOMEM the feature stays off.
+ *     pv_pitchmap_set(h, NULL, NULL, 0, 0) clears the pitch map and its stretch map; a later
+ *     pv_timemap_set by the caller, or its clear, turns the pitch map off too.
+ *   pv_pitchmap_output_length: pv_output_length(h, n); 0 without a pitch map or for NULL.
+ *   pv_pitchmap_process is exactly pv_timemap_process into the scratch rows, then pv_varresample
+ *     into out: pv_timemap_process's arguments, `spec` semantics, capture conditions and
+ *     refusals, plus PV_ERR_ARG without a pitch map.  Launches: pv_timemap_process's, then
+ *     var_resample.  pv_set_phase_lock composes.  With ratio = 1 throughout it is
+ *     pv_timemap_process of pos, bit for bit.
+ * One map for all channels.  pv_rt, the harmoniser, the stream segments and the envelope warp
+ * have no pitch map.  pv_process and every other entry point are unchanged by one. */
+pv_status pv_pitchmap_plan(int n_samps, int hop, const double* pos, const double* ratio, int n, double* pos_s,
+                           int cap_s, int* n_s, long long* step, int cap_steps, int* n_steps);
+pv_status pv_pitchmap_set(pv_handle* h, const double* pos, const double* ratio, int n, int quality);
+long long pv_pitchmap_output_length(const pv_handle* h);
+pv_status pv_pitchmap_process(pv_handle* h, const float* x, long long ldx, long long n_samples, int channels,
+                              int frames, pv_float2* spec, long long ld_spec, float* out, long long ldo,
+                              void* stream);
 
 /* ---------------------------------------------------------------- real-time mode
  * A pv_rt streams `channels` mono channels through the STANDARD pipeline one callback at a

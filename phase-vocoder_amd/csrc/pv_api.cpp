@@ -275,6 +275,7 @@ void pv_destroy(pv_handle* h) {
     if (!h) return;
     DeviceGuard g(h->cfg.device);
     pv_resampler_destroy(h->pitch_rs);
+    pv_varresampler_destroy(h->pmap_vr);
     for (size_t i = 0; i < h->prof.ev_start.size(); ++i)
         if (!h->prof.ev_shared[i]) (void)hipEventDestroy(h->prof.ev_start[i]);
     for (auto e : h->prof.ev_stop) (void)hipEventDestroy(e);

@@ -44,22 +44,9 @@ pv_status reserve(pv_handle* h) {
 
 }  // namespace
 
-}  // namespace pvhost
-
-using namespace pvhost;
-
-extern "C" {
-
-pv_status pv_timemap_split(const double* pos, int n, int* idx, float* frac) {
-    if (!pos || !idx || !frac) return fail(PV_ERR_ARG, "pv_timemap_split: null argument");
-    if (n <= 0) return fail(PV_ERR_ARG, "pv_timemap_split: n must be positive");
-    if (!timemap_split(pos, n, idx, frac))
-        return fail(PV_ERR_ARG, "pv_timemap_split: every position must be finite, >= 0 and < 2^30");
-    return PV_OK;
-}
-
-pv_status pv_timemap_set(pv_handle* h, const double* pos, int n_out) {
-    pv_status st = check_handle("pv_timemap_set", h);
+pv_status timemap_set(const char* fn_, pv_handle* h, const double* pos, int n_out) {
+    const std::string fn(fn_);
+    pv_status st = check_handle(fn_, h);
     if (st != PV_OK) return st;
     DeviceGuard g(h->cfg.device);
     if (!pos && n_out == 0) {  // clear (the calls enqueued before it have read their map)
@@ -67,13 +54,13 @@ pv_status pv_timemap_set(pv_handle* h, const double* pos, int n_out) {
         h->map_imax = 0;
         return PV_OK;
     }
-    if (!pos) return fail(PV_ERR_ARG, "pv_timemap_set: null positions");
+    if (!pos) return fail(PV_ERR_ARG, fn + ": null positions");
     if (n_out < 1 || n_out > h->cfg.max_frames)
-        return fail(PV_ERR_ARG, "pv_timemap_set: n_out must be in [1, max_frames]");
+        return fail(PV_ERR_ARG, fn + ": n_out must be in [1, max_frames]");
     std::vector<int> idx(n_out);
     std::vector<float> frac(n_out);
     if (!timemap_split(pos, n_out, idx.data(), frac.data()))
-        return fail(PV_ERR_ARG, "pv_timemap_set: every position must be finite, >= 0 and < 2^30");
+        return fail(PV_ERR_ARG, fn + ": every position must be finite, >= 0 and < 2^30");
     std::vector<pv::MapEntry> map(n_out);
     for (int u = 0; u < n_out; ++u) map[u] = pv::MapEntry{idx[u], frac[u]};
     // ordered like the compute calls: the calls enqueued before this one (on any stream) have
@@ -87,31 +74,30 @@ pv_status pv_timemap_set(pv_handle* h, const double* pos, int n_out) {
     return PV_OK;
 }
 
-int pv_timemap_frames(const pv_handle* h) { return h ? h->map_n : 0; }
-
-pv_status pv_timemap_process(pv_handle* h, const float* x, long long ldx, long long n_samples, int channels,
-                             int frames, pv_float2* spec, long long ld_spec, float* out, long long ldo,
-                             void* stream) {
-    pv_status st = check_handle("pv_timemap_process", h);
-    if (st != PV_OK || (st = check_common(h, channels, frames)) != PV_OK) return st;
-    if (channels == 0) return PV_OK;
-    if (h->map_n < 1) return fail(PV_ERR_ARG, "pv_timemap_process: no map (pv_timemap_set first)");
-    if (h->transient)
-        return fail(PV_ERR_ARG, "pv_timemap_process: not while the transient phase reset is on (pv_set_transient)");
+pv_status timemap_check(const char* fn_, const pv_handle* h, const float* x, int channels, int frames,
+                        const float* out, long long ldo) {
+    const std::string fn(fn_);
+    if (h->map_n < 1) return fail(PV_ERR_ARG, fn + ": no map (pv_timemap_set first)");
+    if (h->transient) return fail(PV_ERR_ARG, fn + ": not while the transient phase reset is on (pv_set_transient)");
     if (h->pitch_formant)
-        return fail(PV_ERR_ARG, "pv_timemap_process: not while the envelope warp is on (pv_pitch_set_formant)");
-    if (frames < 1) return fail(PV_ERR_ARG, "pv_timemap_process: frames must be at least 1");
+        return fail(PV_ERR_ARG, fn + ": not while the envelope warp is on (pv_pitch_set_formant)");
+    if (frames < 1) return fail(PV_ERR_ARG, fn + ": frames must be at least 1");
     // every row the kernels read, i_u and (for i_u < frames - 1) i_u + 1, is an analysed one
     if (h->map_imax > frames - 1)
-        return fail(PV_ERR_ARG, "pv_timemap_process: the map reads past the last analysed frame (max floor(pos) > frames - 1)");
+        return fail(PV_ERR_ARG, fn + ": the map reads past the last analysed frame (max floor(pos) > frames - 1)");
     if (!x || !out) return fail(PV_ERR_ARG, "null x/out");
+    if (channels > 1 && ldo < pv_output_length(h, h->map_n))
+        return fail(PV_ERR_ARG, "ldo < pv_output_length(h, pv_timemap_frames(h))");
+    return PV_OK;
+}
+
+pv_status timemap_launch(const char* fn, pv_handle* h, const float* x, long long ldx, long long n_samples,
+                         int channels, int frames, pv_float2* spec, long long ld_spec, float* out, long long ldo,
+                         hipStream_t s) {
+    pv_status st;
     const int n_out = h->map_n;
     const long long olen = pv_output_length(h, n_out);
-    if (channels > 1 && ldo < olen) return fail(PV_ERR_ARG, "ldo < pv_output_length(h, pv_timemap_frames(h))");
-    DeviceGuard g(h->cfg.device);
-    ProfCall pc_(h);
-    hipStream_t s = (hipStream_t)stream;
-    if (!spec && (st = own_spectrum(h, "pv_timemap_process", s, &spec, &ld_spec)) != PV_OK) return st;
+    if (!spec && (st = own_spectrum(h, fn, s, &spec, &ld_spec)) != PV_OK) return st;
     // every bin analysed (a time stretch reads them all); no run records: the scan is the map's
     if ((st = do_analysis(h, x, ldx, n_samples, channels, frames, spec, ld_spec, false, s)) != PV_OK) return st;
 
@@ -141,6 +127,45 @@ pv_status pv_timemap_process(pv_handle* h, const float* x, long long ldx, long l
     pv::set_map_args(&p, pv::MapArgs{h->d_map, frames});
     PV_LAUNCH(h, KSM, s, pv::launch_synthesis_map(h->L_syn, h->phase_lock, channels, p, s));
     return do_seam(h, channels, n_out, nullptr, 0, out, ldo, olen, s);
+}
+
+pv_status timemap_handle_check(const char* fn, const pv_handle* h) { return check_handle(fn, h); }
+
+}  // namespace pvhost
+
+using namespace pvhost;
+
+extern "C" {
+
+pv_status pv_timemap_split(const double* pos, int n, int* idx, float* frac) {
+    if (!pos || !idx || !frac) return fail(PV_ERR_ARG, "pv_timemap_split: null argument");
+    if (n <= 0) return fail(PV_ERR_ARG, "pv_timemap_split: n must be positive");
+    if (!timemap_split(pos, n, idx, frac))
+        return fail(PV_ERR_ARG, "pv_timemap_split: every position must be finite, >= 0 and < 2^30");
+    return PV_OK;
+}
+
+pv_status pv_timemap_set(pv_handle* h, const double* pos, int n_out) {
+    const pv_status st = timemap_set("pv_timemap_set", h, pos, n_out);
+    // the map is the caller's again: a pitch map (pv_pitchmap_set), whose stretch map this replaces
+    // or clears, is off
+    if (st == PV_OK) h->pmap_n = 0;
+    return st;
+}
+
+int pv_timemap_frames(const pv_handle* h) { return h ? h->map_n : 0; }
+
+pv_status pv_timemap_process(pv_handle* h, const float* x, long long ldx, long long n_samples, int channels,
+                             int frames, pv_float2* spec, long long ld_spec, float* out, long long ldo,
+                             void* stream) {
+    pv_status st = check_handle("pv_timemap_process", h);
+    if (st != PV_OK || (st = check_common(h, channels, frames)) != PV_OK) return st;
+    if (channels == 0) return PV_OK;
+    if ((st = timemap_check("pv_timemap_process", h, x, channels, frames, out, ldo)) != PV_OK) return st;
+    DeviceGuard g(h->cfg.device);
+    ProfCall pc_(h);
+    return timemap_launch("pv_timemap_process", h, x, ldx, n_samples, channels, frames, spec, ld_spec, out, ldo,
+                          (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -12,6 +12,7 @@
 #include "pv_kernels.h"
 #include "pv_resample.hpp"
 #include "pv_tables.hpp"
+#include "pv_varresample.hpp"
 
 #pragma GCC visibility push(hidden)
 namespace pvhost {
@@ -31,12 +32,12 @@ pv_status fail(pv_status s, const std::string& msg);
 
 // kernel ids of the per-launch profile and their names (pv_profile_read), index for index
 enum { KA, KRS, KC, KS, KSEAM, KCA, KRT, KF, KSL, KENV, KSF, KRES, KRTR, KSW, KON, KPK, KRST, KSR, KMS, KMC, KSM,
-       kNumKernels };
+       KVR, kNumKernels };
 inline constexpr const char* kKernelNames[] = {"analysis", "runsum", "carry", "synthesis", "seam",
                                                "compat_analysis", "rt", "fused", "synthesis_locked",
                                                "envelope", "synthesis_formant", "resample", "rt_resample",
                                                "synthesis_warp", "onset", "pick", "reset", "synthesis_reset",
-                                               "map_sum", "map_carry", "synthesis_map"};
+                                               "map_sum", "map_carry", "synthesis_map", "var_resample"};
 static_assert(sizeof(kKernelNames) / sizeof(kKernelNames[0]) == kNumKernels, "one name per kernel id");
 
 // Move-only owner of one hipMalloc (Pinned: hipHostMalloc, device-mapped) allocation.  Converts
@@ -153,6 +154,11 @@ struct pv_handle {
     int map_n = 0, map_imax = 0;
     pvhost::DevBuf<pv::MapEntry> d_map;
     pvhost::DevBuf<unsigned> d_map_sum, d_map_carry;
+    // pv_pitchmap_set: the variable-rate resampler of pv_pitchmap_process (blocks of hop samples)
+    // and the final frames n of the pitch map (0: no pitch map; the time map is then the
+    // caller's).  The stretch writes the scratch rows of pv_pitch_process, d_pitch.
+    pv_varresampler* pmap_vr = nullptr;
+    int pmap_n = 0;
     float scale = 1.0f, rho = 1.0f, inv_q = 1.0f;
     unsigned long long p_mod = 0, q = 1;
     int q_pow2 = 1;
@@ -214,6 +220,19 @@ struct pv_resampler {
     int P = 1, Q = 1, quality = 0, device = 0;
     pv::ResamplePlan plan{};
     pvhost::DevBuf<float4> d_tab;  // nullptr at ratio 1: the rows are copied
+};
+
+// pv_varresampler: a quality preset, the block length and the device records of the current map
+// (pv_varresample.hpp)
+struct pv_varresampler {
+    int quality = 0, block = 0, max_blocks = 0, device = 0;
+    int nblocks = 0;        // 0: no map
+    int copy = 0;           // every step 2^32, no fraction: the rows shifted by copy_shift samples
+    long long copy_shift = 0;
+    int span4_max = 0;      // the largest staged span of the map's tiles
+    pvhost::DevBuf<pv::VarBlock> d_blocks;  // [max_blocks], zeroed
+    pvhost::DevBuf<pv::VarTile> d_tiles;    // [ceil(max_blocks block / kVarTile)], zeroed
+    pvhost::DevBuf<float2> d_win;           // [kVarWinN + 1]
 };
 
 namespace pvhost {
@@ -320,6 +339,23 @@ pv_status transient_offsets(pv_handle* h, const pv_float2* spec, long long ld_sp
 // the launch of pv_resample / pv_pitch_process (arguments checked by the caller)
 hipError_t resample_rows(const pv_resampler* rs, const float* x, long long ldx, long long n_in, int channels,
                          float* y, long long ldy, hipStream_t s);
+
+// ---- time map (pv_api_timemap.cpp): pv_timemap_set and pv_timemap_process under the name of
+// the entry point that calls them (pv_pitchmap_set installs its stretch map through the first;
+// pv_pitchmap_process runs the second into the scratch rows): the handle's kind, the refusals of a
+// call with channels > 0, and the launches (the caller holds the device guard and the profile call)
+pv_status timemap_set(const char* fn, pv_handle* h, const double* pos, int n_out);
+pv_status timemap_handle_check(const char* fn, const pv_handle* h);
+pv_status timemap_check(const char* fn, const pv_handle* h, const float* x, int channels, int frames,
+                        const float* out, long long ldo);
+pv_status timemap_launch(const char* fn, pv_handle* h, const float* x, long long ldx, long long n_samples,
+                         int channels, int frames, pv_float2* spec, long long ld_spec, float* out, long long ldo,
+                         hipStream_t s);
+
+// ---- variable-rate resampler (pv_api_varresample.cpp)
+// the launch of pv_varresample / pv_pitchmap_process (arguments checked by the caller)
+hipError_t varresample_rows(const pv_varresampler* vr, const float* x, long long ldx, long long n_in, int channels,
+                            float* y, long long ldy, long long n_out, hipStream_t s);
 
 }  // namespace pvhost
 #pragma GCC visibility pop

@@ -390,4 +390,69 @@ long long resample_length(int P, int Q, long long n_in) {
     return (n_in * Q + P - 1) / P;
 }
 
+// ---- variable-rate resampler (pv_varresample_*)
+bool varresample_steps(const double* ratio, int n, long long* step) {
+    for (int k = 0; k < n; ++k) {
+        const double r = ratio[k];
+        if (!std::isfinite(r) || r < 0.25 || r > 4.0) return false;
+        step[k] = std::llrint(r * 4294967296.0);
+    }
+    return true;
+}
+
+// Sq: the largest even integer <= rolloff min(1, 2^32 / d) 2^32; W = ceil(Z / (Sq / 2^32))
+void var_block_filter(long long d, int quality, unsigned* Sq, int* W) {
+    const double v = kResamplePresets[quality][1] * std::min(1.0, 4294967296.0 / (double)d) * 4294967296.0;
+    const unsigned sq = (unsigned)std::floor(v) & ~1u;
+    *Sq = sq;
+    *W = (int)std::ceil(kResamplePresets[quality][0] / ((double)sq / 4294967296.0));
+}
+
+double resample_zero_crossings(int quality) { return kResamplePresets[quality][0]; }
+
+// the Kaiser window over u = i / n with the sinc's 1 / pi: {w(u_i) / pi, the rise to the next
+// entry} for i < n (each value rounded to fp32 first: the interpolation ends on the next entry),
+// then {0, 0} up to `len` entries
+void var_window_table(int quality, int n, int len, std::vector<float>& tab) {
+    const double beta = kResamplePresets[quality][2], i0b = bessel_i0(beta);
+    std::vector<float> w(n + 1);
+    for (int i = 0; i <= n; ++i) {
+        const double u = (double)i / (double)n;
+        w[i] = (float)(bessel_i0(beta * std::sqrt(std::max(0.0, 1.0 - u * u))) / i0b / kPi);
+    }
+    tab.assign(2 * (size_t)len, 0.0f);
+    for (int i = 0; i < n; ++i) {
+        tab[2 * i] = w[i];
+        tab[2 * i + 1] = w[i + 1] - w[i];
+    }
+}
+
+// The pitch map's plan (pv_pitchmap_plan): the time map of the stretch and the steps of the
+// resampling after it.  Integers and fp64 only.
+bool pitchmap_plan(int N, int hop, const double* pos, const double* ratio, int n, std::vector<double>& pos_s,
+                   std::vector<long long>& step) {
+    if (n < 1 || hop < 1 || N < hop || (long long)n * hop >= (1LL << 28)) return false;
+    for (int u = 0; u < n; ++u)
+        if (!std::isfinite(pos[u]) || pos[u] < 0.0 || pos[u] >= 1073741824.0) return false;
+    const long long L = (long long)n * hop + N - hop;
+    const long long nb = (L + hop - 1) / hop;
+    step.assign((size_t)nb, 0);
+    if (!varresample_steps(ratio, n, step.data())) return false;
+    for (long long b = n; b < nb; ++b) step[(size_t)b] = step[(size_t)n - 1];
+    std::vector<long long> S((size_t)n + 1, 0);  // Sigma_0 .. Sigma_n < 2^28 2^34 = 2^62
+    for (int b = 0; b < n; ++b) S[b + 1] = S[b] + (long long)hop * step[b];
+    const long long unit = (long long)hop << 32;
+    const long long n_s = std::max(1LL, (S[n] + unit - 1) / unit);
+    pos_s.assign((size_t)n_s, 0.0);
+    int b = 0;
+    for (long long v = 0; v < n_s; ++v) {
+        const long long t = v * unit;
+        while (b < n - 1 && t >= S[b + 1]) ++b;
+        const double w = (double)(t - S[b]) / (double)(S[b + 1] - S[b]);
+        const double p0 = pos[b], p1 = pos[std::min(b + 1, n - 1)];
+        pos_s[(size_t)v] = p0 + w * (p1 - p0);
+    }
+    return true;
+}
+
 }  // namespace pvtab

@@ -94,5 +94,18 @@ int resample_half_width(int P, int Q, int quality);
 void resample_row(int P, int Q, int quality, int W, int r, float* row);
 long long resample_length(int P, int Q, long long n_in);
 
+// ---- variable-rate resampler and pitch map (include/pv.h)
+constexpr long long kVarOne = 1LL << 32, kVarStepMin = 1LL << 30, kVarStepMax = 1LL << 34;
+// d = llrint(ratio 2^32); false on a ratio that is not finite or outside [1/4, 4]
+bool varresample_steps(const double* ratio, int n, long long* step);
+// a block's cutoff Sq (even, s = Sq / 2^32) and half width W for its step d
+void var_block_filter(long long d, int quality, unsigned* Sq, int* W);
+double resample_zero_crossings(int quality);  // Z of the preset
+// the kernel's window table: n intervals over |u| in [0, 1], `len` > n entries {value / pi, rise}
+void var_window_table(int quality, int n, int len, std::vector<float>& tab);
+// pos, ratio [n] -> pos_s [n_s], step [ceil((n hop + N - hop) / hop)]; false on a bad argument
+bool pitchmap_plan(int N, int hop, const double* pos, const double* ratio, int n, std::vector<double>& pos_s,
+                   std::vector<long long>& step);
+
 }  // namespace pvtab
 #pragma GCC visibility pop

@@ -35,6 +35,10 @@
 //                                        effect t at scale 1 (--scale is ignored), every channel in
 //                                        one call; composes with --phase-lock; not with --rt,
 //                                        --transients or --pitch-resample
+//     --pitch-glide R0 R1                pitch map (pv_pitchmap_process): the pitch ratio glides
+//                                        geometrically from R0 to R1 (each in [1/4, 4]) over the
+//                                        output while the tempo follows --rate R (default 1);
+//                                        refuses what --rate refuses
 //     --single-arg                       PhaseVocoder(N): periodic Hann, hop N/2 (phaseVocoder.h:46-78)
 //     --nan-faithful                     atanf(0/0) = NaN phases as the reference (kernel.cu:101-109)
 //     --timer                            print CudaPhase::timer() per call (main.cpp:238-241, 275-278)
@@ -56,6 +60,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -104,6 +109,8 @@ int main(int argc, char** argv) {
     float transient_thr = 0.0f;  // 0: PV_TRANSIENT_DEFAULT_THRESHOLD
     int pitch_resample = -1;  // --pitch-resample: quality preset (0 fast, 1 best)
     double rate = 0.0;        // --rate: the time map's playback rate (0: no map)
+    bool glide = false;       // --pitch-glide: the pitch map's ratio from glide0 to glide1
+    double glide0 = 1.0, glide1 = 1.0;
     double ana_ms = 0.0, syn_ms = 0.0;
     pv_mode mode = PV_MODE_REF_COMPAT;
     std::vector<std::string> pos;
@@ -140,6 +147,15 @@ int main(int argc, char** argv) {
                 return 1;
             }
         }
+        else if (a == "--pitch-glide" && i + 2 < argc) {
+            glide0 = std::atof(argv[++i]);
+            glide1 = std::atof(argv[++i]);
+            if (!(glide0 >= 0.25 && glide0 <= 4.0 && glide1 >= 0.25 && glide1 <= 4.0)) {
+                std::fprintf(stderr, "err: --pitch-glide R0 R1, each in [1/4, 4]\n");
+                return 1;
+            }
+            glide = true;
+        }
         else if (a == "--pitch-formant" && i + 1 < argc) pitch_formant = std::atoi(argv[++i]);
         else if (a == "--pitch-resample" && i + 1 < argc) {
             const std::string q = argv[++i];
@@ -172,11 +188,12 @@ int main(int argc, char** argv) {
         scale = 1.0f;
         mode = PV_MODE_REF_COMPAT;
     }
+    if (glide && !(rate > 0.0)) rate = 1.0;  // the pitch map's tempo curve: --rate, or the input's own
     if (rate > 0.0) {
         if (rt || transients || pitch_resample >= 0 || pitch_formant != 0 || single_arg || mode != PV_MODE_STANDARD ||
             effect != TIME_SHIFT) {
-            std::fprintf(stderr, "err: --rate needs --mode std with effect t (not --rt, --transients, --pitch-resample, "
-                         "--single-arg)\n");
+            std::fprintf(stderr, "err: %s needs --mode std with effect t (not --rt, --transients, --pitch-resample, "
+                         "--single-arg)\n", glide ? "--pitch-glide" : "--rate");
             return 1;
         }
         scale = 1.0f;  // the map replaces the scale
@@ -189,7 +206,13 @@ int main(int argc, char** argv) {
     if (rate > 0.0)
         for (long long u = 0; frames > 0 && (double)u * rate <= (double)(frames - 1) + 1e-9 && u < (1LL << 24); ++u)
             map_pos.push_back(std::min((double)u * rate, (double)(frames - 1)));
-    const int cap = std::max(frames + numSamples / std::max(1, (int)(scale * hop)) + 2, (int)map_pos.size());
+    // the pitch map: the ratio of output frame u, and the frames its stretch may need
+    std::vector<double> map_ratio;
+    if (glide)
+        for (size_t u = 0; u < map_pos.size(); ++u)
+            map_ratio.push_back(glide0 * std::pow(glide1 / glide0, map_pos.size() > 1 ? (double)u / (double)(map_pos.size() - 1) : 0.0));
+    const int cap = std::max(frames + numSamples / std::max(1, (int)(scale * hop)) + 2,
+                             (int)map_pos.size() * (glide ? 4 : 1) + (glide ? 2 : 0));
     std::unique_ptr<PhaseVocoder> owner(
         single_arg ? new PhaseVocoder(N, numChannels > 0 ? numChannels : 1, cap)  // phaseVocoder.h:46
                    : new PhaseVocoder(N, effect, scale, hopdiv, mode, numChannels > 0 ? numChannels : 1, cap));
@@ -249,7 +272,12 @@ int main(int argc, char** argv) {
             return 1;
         }
     }
-    if (rate > 0.0 && !map_pos.empty() &&
+    if (glide && !map_pos.empty() &&
+        pv_pitchmap_set(phase.handle, map_pos.data(), map_ratio.data(), (int)map_pos.size(), 0) != PV_OK) {
+        std::fprintf(stderr, "err: --pitch-glide: %s\n", pv_last_error());
+        return 1;
+    }
+    if (!glide && rate > 0.0 && !map_pos.empty() &&
         pv_timemap_set(phase.handle, map_pos.data(), (int)map_pos.size()) != PV_OK) {
         std::fprintf(stderr, "err: --rate: %s\n", pv_last_error());
         return 1;
@@ -310,7 +338,11 @@ int main(int argc, char** argv) {
         const long long olen = outLen;
         float* d_out = nullptr;
         HIPCHECK(hipMalloc((void**)&d_out, sizeof(float) * (size_t)std::max(olen, 1LL) * std::max(numChannels, 1)));
-        if (olen > 0)
+        if (olen > 0 && glide)
+            PhaseVocoder::checkCUDAErrori(pv_pitchmap_process(phase.handle, d_input, padN, numSamples, numChannels,
+                                                              frames, nullptr, 0, d_out, olen, nullptr),
+                                          "pv_pitchmap_process", __LINE__);
+        else if (olen > 0)
             PhaseVocoder::checkCUDAErrori(pv_timemap_process(phase.handle, d_input, padN, numSamples, numChannels,
                                                              frames, nullptr, 0, d_out, olen, nullptr),
                                           "pv_timemap_process", __LINE__);

@@ -6,6 +6,8 @@ from .vocoder import (PITCH_SHIFT, REF_COMPAT, STANDARD, TIME_SHIFT,  # noqa: F4
 from .realtime import RealTimeVocoder  # noqa: F401
 from .harmonizer import Harmonizer  # noqa: F401
 from .resample import Resampler  # noqa: F401
+from .varresample import VarResampler, pitch_map_plan, ratio_steps  # noqa: F401
 
 __all__ = ["PhaseVocoder", "PVError", "TIME_SHIFT", "PITCH_SHIFT", "REF_COMPAT", "STANDARD", "RealTimeVocoder", "Harmonizer",
-           "Resampler", "frame_count", "lib", "rate_map", "timemap_split"]
+           "Resampler", "VarResampler", "frame_count", "lib", "pitch_map_plan", "rate_map", "ratio_steps",
+           "timemap_split"]

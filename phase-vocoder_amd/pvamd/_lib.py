@@ -230,6 +230,26 @@ def lib():
     L.pv_timemap_frames.restype = i
     L.pv_timemap_process.argtypes = [vp, vp, ll, ll, i, i, vp, ll, vp, ll, vp]
     L.pv_timemap_process.restype = i
+    L.pv_varresampler_create.argtypes = [i, i, i, i, ctypes.POINTER(vp)]
+    L.pv_varresampler_create.restype = i
+    L.pv_varresampler_destroy.argtypes = [vp]
+    L.pv_varresampler_destroy.restype = None
+    L.pv_varresample_steps.argtypes = [vp, i, vp]
+    L.pv_varresample_steps.restype = i
+    L.pv_varresampler_set_map.argtypes = [vp, ll, vp, i]
+    L.pv_varresampler_set_map.restype = i
+    L.pv_varresample_length.argtypes = [vp]
+    L.pv_varresample_length.restype = ll
+    L.pv_varresample.argtypes = [vp, vp, ll, ll, i, vp, ll, ll, vp]
+    L.pv_varresample.restype = i
+    L.pv_pitchmap_plan.argtypes = [i, i, vp, vp, i, vp, i, ctypes.POINTER(i), vp, i, ctypes.POINTER(i)]
+    L.pv_pitchmap_plan.restype = i
+    L.pv_pitchmap_set.argtypes = [vp, vp, vp, i, i]
+    L.pv_pitchmap_set.restype = i
+    L.pv_pitchmap_output_length.argtypes = [vp]
+    L.pv_pitchmap_output_length.restype = ll
+    L.pv_pitchmap_process.argtypes = [vp, vp, ll, ll, i, i, vp, ll, vp, ll, vp]
+    L.pv_pitchmap_process.restype = i
     _lib = L
     return L
 

@@ -425,6 +425,51 @@ class PhaseVocoder:
                                               out.stride(0), self._stream(stream)), "pv_timemap_process")
         return out, spec
 
+    # -------------------------------------------------------------- pitch map
+    def set_pitch_map(self, positions, ratios=None, quality: int = 0):
+        """pv_pitchmap_set: final output frame u of `pitch_map_process` sounds at the analysis
+        position positions[u] (the tempo curve, as `set_time_map`'s) with its pitch moved by
+        ratios[u] (1/4 .. 4): a glide, a vibrato, a correction curve, tempo and pitch varying
+        independently.  It installs the time map of the stretch (`time_map_frames` then reads its
+        length) and the handle's variable-rate resampler (quality 0 fast, 1 best).  One map for
+        all channels; a setup call.  positions=None clears it; so does a later `set_time_map`."""
+        if positions is None:
+            self._call(self._L.pv_pitchmap_set(self._h, None, None, 0, 0), "pv_pitchmap_set")
+            return
+        pos = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1)
+        rat = np.ascontiguousarray(ratios, dtype=np.float64).reshape(-1)
+        if pos.size != rat.size:
+            raise ValueError("positions and ratios must have one entry per output frame each")
+        vp = ctypes.c_void_p
+        self._call(self._L.pv_pitchmap_set(self._h, pos.ctypes.data_as(vp), rat.ctypes.data_as(vp), int(pos.size),
+                                           int(quality)), "pv_pitchmap_set")
+
+    @property
+    def pitch_map_output_length(self) -> int:
+        return int(self._L.pv_pitchmap_output_length(self._h))
+
+    def pitch_map_process(self, x, frames: int | None = None, n_samples: int | None = None, spec=None,
+                          out=None, stream=None, spectrum: bool = True):
+        """pv_pitchmap_process: `time_map_process` with the pitch map's stretch map into the
+        handle's scratch rows, then the variable-rate resampling -> (out [C,
+        pitch_map_output_length], spec), as `process` does."""
+        torch = _torch()
+        x = self._as2d(x)
+        C, n = x.shape
+        n_samples = n if n_samples is None else n_samples
+        frames = self.num_frames(n_samples) if frames is None else frames
+        if not spectrum and spec is not None:
+            raise ValueError("spectrum=False with a spec buffer")
+        if spectrum and spec is None:
+            spec = self.alloc_spec(C, frames)
+        if out is None:
+            out = torch.empty((C, self.pitch_map_output_length), dtype=torch.float32, device=f"cuda:{self.device}")
+        self._call(self._L.pv_pitchmap_process(self._h, _ptr(x), x.stride(0), n_samples, C, frames,
+                                               _ptr(spec) if spec is not None else None,
+                                               spec.stride(0) // 2 if spec is not None else 0, _ptr(out),
+                                               out.stride(0), self._stream(stream)), "pv_pitchmap_process")
+        return out, spec
+
     # -------------------------------------------------------------- pitch shift by resampling
     def reserve_pitch(self, quality: int = 0):
         """pv_pitch_reserve: build the handle's resampler (ratio outHopSize / hopSize; quality 0
