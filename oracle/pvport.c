@@ -263,7 +263,8 @@ static void cport_free(cport_ctx* c) {
     free(c->S); free(c->Z);
 }
 
-static void cport_channel(cport_ctx* c, const float* x, long n, int frames, float* out) {
+/* hs: the overlap-add hop, (int)(timeScale * hop) (pvref.c pvr_compat_process_hs); hop at scale 1 */
+static void cport_channel(cport_ctx* c, const float* x, long n, int frames, int hs, float* out) {
     const int N = c->N, L = N / 2, hop = c->hop;
     memset(c->back, 0, sizeof(float) * N);
     for (int t = 0; t < frames; ++t) {
@@ -275,11 +276,14 @@ static void cport_channel(cport_ctx* c, const float* x, long n, int frames, floa
             c->xw[k + N / 2 + N] = c->fr[k] * c->w[k];
         }
         pvr_rfft_c32(c->xw, 2 * N, c->tw2, c->tws2, c->X, c->work);
-        /* magnitude and atanf(y / x) of bins 0 .. N; bins N+1 .. 2N-1 mirror them */
+        /* magnitude and atanf(y / x) of bins 0 .. N; bins N+1 .. 2N-1 mirror them.  An
+         * all-zero bin has phase 0, the defined deviation of pvr_compat_analysis_frame and the
+         * GPU (not the reference's atanf(0 / 0) = NaN): in fp32 a bin of a square wave can
+         * cancel to exactly 0 + 0i where the fp64 oracle keeps a residue */
         for (int k = 0; k <= N; ++k) {
             const float re = c->X[k].x, im = c->X[k].y;
             c->S[k].x = sqrtf(re * re + im * im);
-            c->S[k].y = atanf(im / re);
+            c->S[k].y = (re == 0.0f && im == 0.0f) ? 0.0f : atanf(im / re);
         }
         for (int k = N + 1; k < 2 * N; ++k) { c->S[k].x = c->S[2 * N - k].x; c->S[k].y = -c->S[2 * N - k].y; }
         /* cudaTimeScale (timeScale 1): x' = m cos(phi), y' = x' sin(phi); bins 0 .. N/2 */
@@ -305,15 +309,15 @@ static void cport_channel(cport_ctx* c, const float* x, long n, int frames, floa
         /* /N, swap halves, window; overlap-add with the running back frame, emit hop */
         const float invN = 1.0f / (float)N;
         for (int k = 0; k < N; ++k) c->front[k] = c->y[(k + L) % N] * invN * c->w[k];
-        for (int k = hop; k < N; ++k) c->front[k - hop] += c->back[k];
-        for (int j = 0; j < hop; ++j) out[start + j] = c->front[j];
+        for (int k = hs; k < N; ++k) c->front[k - hs] += c->back[k];
+        for (int j = 0; j < hs; ++j) out[(long)t * hs + j] = c->front[j];
         memcpy(c->back, c->front, sizeof(float) * N);
     }
-    for (int k = hop; k < N; ++k) out[(long)frames * hop + (k - hop)] = c->back[k];
+    for (int k = hs; k < N; ++k) out[(long)frames * hs + (k - hs)] = c->back[k];
 }
 
-int pvr_port_compat_process_batch(const float* x, long ldx, long n, int C, int N, int hop_div,
-                                  int frames, float* out, long ldo, int threads) {
+int pvr_port_compat_process_hs_batch(const float* x, long ldx, long n, int C, int N, int hop_div,
+                                     int hs, int frames, float* out, long ldo, int threads) {
     int used = 1;
 #ifdef _OPENMP
     if (threads > 0) omp_set_num_threads(threads);
@@ -324,15 +328,20 @@ int pvr_port_compat_process_batch(const float* x, long ldx, long n, int C, int N
         cport_ctx c;
         cport_init(&c, N, hop_div);
 #pragma omp for schedule(dynamic, 1)
-        for (int ch = 0; ch < C; ++ch) cport_channel(&c, x + (size_t)ch * ldx, n, frames, out + (size_t)ch * ldo);
+        for (int ch = 0; ch < C; ++ch) cport_channel(&c, x + (size_t)ch * ldx, n, frames, hs, out + (size_t)ch * ldo);
         cport_free(&c);
     }
 #else
     (void)threads;
     cport_ctx c;
     cport_init(&c, N, hop_div);
-    for (int ch = 0; ch < C; ++ch) cport_channel(&c, x + (size_t)ch * ldx, n, frames, out + (size_t)ch * ldo);
+    for (int ch = 0; ch < C; ++ch) cport_channel(&c, x + (size_t)ch * ldx, n, frames, hs, out + (size_t)ch * ldo);
     cport_free(&c);
 #endif
     return used;
+}
+
+int pvr_port_compat_process_batch(const float* x, long ldx, long n, int C, int N, int hop_div,
+                                  int frames, float* out, long ldo, int threads) {
+    return pvr_port_compat_process_hs_batch(x, ldx, n, C, N, hop_div, N / hop_div, frames, out, ldo, threads);
 }

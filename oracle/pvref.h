@@ -128,6 +128,10 @@ int pvr_port_std_process_batch(const float* x, long ldx, long n, int C, int N, i
 /* the fp32 CPU port of REF_COMPAT (oracle/pvport.c, the compat line's cpu_baseline) */
 int pvr_port_compat_process_batch(const float* x, long ldx, long n, int C, int N, int hop_div,
                                   int frames, float* out, long ldo, int threads);
+/* the same at the out hop hs of a time scale (as pvr_compat_process_hs): out rows hold
+ * frames * hs + (N - hs) samples, 0 < hs <= N */
+int pvr_port_compat_process_hs_batch(const float* x, long ldx, long n, int C, int N, int hop_div,
+                                     int hs, int frames, float* out, long ldo, int threads);
 /* REF_COMPAT (pvr_compat_process, the 4-argument constructor's Hamming) per channel */
 int pvr_compat_process_batch(const float* x, long ldx, long n, int C, int N, int hop_div,
                              int frames, float* out, long ldo, int threads);

@@ -81,6 +81,9 @@ def lib():
         L.pvr_compat_process_batch.restype = c_int
         L.pvr_port_compat_process_batch.argtypes = L.pvr_compat_process_batch.argtypes
         L.pvr_port_compat_process_batch.restype = c_int
+        L.pvr_port_compat_process_hs_batch.argtypes = [_f32p, c_long, c_long, c_int, c_int, c_int, c_int, c_int,
+                                                       _f32p, c_long, c_int]
+        L.pvr_port_compat_process_hs_batch.restype = c_int
         _lib = L
     return _lib
 
@@ -237,6 +240,16 @@ def std_process(x, N, hop_div, effect, scale, frames=None):
     return out
 
 
+def std_process_channels(x, N, hop_div, effect, scale, frames=None):
+    """std_process of every row of x [C, n]: the fp64 outputs [C, len] (std_process_batch
+    rounds them to float32), the channels on up to 16 threads."""
+    from concurrent.futures import ThreadPoolExecutor
+    x = _c32(x)
+    lib()
+    with ThreadPoolExecutor(max_workers=max(1, min(16, x.shape[0], os.cpu_count() or 1))) as ex:
+        return np.stack(list(ex.map(lambda row: std_process(row, N, hop_div, effect, scale, frames), x)))
+
+
 def std_process_batch(x, N, hop_div, effect, scale, frames=None, threads=0):
     """x: [C, n] float32. Returns (out [C, len] float32, threads_used)."""
     x = _c32(x)
@@ -282,18 +295,21 @@ def compat_process_batch(x, N, hop_div, frames=None, threads=0):
     return out, used
 
 
-def port_compat_process_batch(x, N, hop_div, frames=None, threads=0):
+def port_compat_process_batch(x, N, hop_div, frames=None, threads=0, out_hop=None):
     """The fp32 CPU port of REF_COMPAT (oracle/pvport.c): x [C, n] float32 -> (out [C, len]
     float32, threads used).  The compat line's cpu_baseline; pinned to compat_process_batch
-    (the fp64 restatement) by the tests."""
+    (the fp64 restatement) by the tests.  out_hop: the overlap-add hop of a time scale, as
+    compat_process's (None = hop)."""
     x = _c32(x)
     C, n = x.shape
     hop = N // hop_div
+    hs = hop if out_hop is None else int(out_hop)
+    assert 0 < hs <= N
     if frames is None:
         frames = num_frames(n, hop)
-    olen = frames * hop + (N - hop)
+    olen = frames * hs + (N - hs)
     out = np.zeros((C, olen), np.float32)
-    used = lib().pvr_port_compat_process_batch(x, n, n, C, N, hop_div, frames, out, olen, int(threads))
+    used = lib().pvr_port_compat_process_hs_batch(x, n, n, C, N, hop_div, hs, frames, out, olen, int(threads))
     return out, used
 
 

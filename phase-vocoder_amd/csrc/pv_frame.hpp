@@ -34,7 +34,9 @@ __device__ __forceinline__ float2 real_split(const float2* tile, const float2* _
 // TWICE: X is returned scaled by exactly 2 (the four halvings dropped).  Scaling by a
 // power of two commutes with every rounding here, so 2X is bit-exactly twice the
 // contract's X and atan2 of it is the contract's phase bit for bit (a = min/max and the
-// sign tests are scale-free); the caller halves the magnitude.
+// sign tests are scale-free); the caller halves the magnitude.  (Outside the denormal range:
+// where a halved sum of the contract is an fp32 denormal it rounds and the doubled one does
+// not, so bins of |X| < 2^-62 can differ from the contract in the last place — DESIGN.md §3.2.)
 template <int L, int CH, bool TWICE = false>
 __device__ __forceinline__ void split_chunk(const float2* tile, const float2* twsl, int lane, int i0,
                                             float2 (&X)[CH]) {

@@ -346,10 +346,13 @@ __global__ __launch_bounds__(256, PV_FUSED_WAVES) void k_fused(FusedParams p) {
                     static_for<0, CH>([&](auto cc) {
                         constexpr int i = i0 + decltype(cc)::value;
                         if constexpr (i <= Geo<LH>::E) {
-                            // X came out doubled (TWICE): Y = X2^2 / (2 |X2|); |X| = 0 -> 0
+                            // X came out doubled (TWICE): Y = X2^2 / (2 |X2|); |X| = 0 -> 0.
+                            // v_rsq_f32 reads a denormal |X2|^2 as zero and returns +inf (0 * inf
+                            // and inf in Y: a frame of NaN in a tail fading through |X| ~ 1e-20),
+                            // so such a bin (|X| < 2^-64) counts as zero too
                             const float2 x2 = X[decltype(cc)::value];
                             const float r = __builtin_fmaf(x2.x, x2.x, x2.y * x2.y);
-                            const float rs = (r > 0.0f) ? __builtin_amdgcn_rsqf(r) : 0.0f;
+                            const float rs = (r >= 0x1p-126f) ? __builtin_amdgcn_rsqf(r) : 0.0f;
                             yh[i] = make_float2(0.5f * __builtin_fmaf(x2.x, x2.x, -(x2.y * x2.y)) * rs,
                                                 x2.x * x2.y * rs);
                         }

@@ -7,6 +7,7 @@ import pytest
 
 import pvref
 from pvamd import PITCH_SHIFT, STANDARD, TIME_SHIFT, PhaseVocoder
+from signals import assert_hop_parity
 from test_gpu_parity import RMS_TOL, rms, synth, to_dev
 
 pytestmark = pytest.mark.gpu
@@ -73,8 +74,12 @@ def test_fused_equals_split_path(cuda, monkeypatch, N, hop_div, effect, scale):
     gf, gs = out_f.cpu().numpy(), out_s.cpu().numpy()
     assert np.abs(gf - gs).max() <= 1e-6
     ref, _ = pvref.std_process_batch(xs, N, hop_div, ord(effect), scale)
+    port, _ = pvref.port_std_process_batch(xs, N, hop_div, ord(effect), scale)
+    ref64 = pvref.std_process_channels(xs, N, hop_div, ord(effect), scale)
     for c in range(C):
         assert rms(gf[c], ref[c]) <= RMS_TOL, f"ch{c}"
+        assert_hop_parity(gf[c], ref64[c], port[c], pf.outHopSize, what=f"fused ch{c}")
+        assert_hop_parity(gs[c], ref64[c], port[c], ps.outHopSize, what=f"split ch{c}")
     # same run length as the split path: bit for bit — for pitch 2 at N >= 512 through the
     # single launch's MODE 3 gather (PV_FUSED_HALF=0); its default half-size resynthesis
     # (MODE 4) is the same sum with other roundings: within 1e-6
@@ -102,6 +107,8 @@ def test_fused_short_and_ragged(cuda, n):
     ref = pvref.std_process(x, 1024, 4, ord("p"), 2.0)
     g = out.cpu().numpy()[0]
     assert g.shape == ref.shape and rms(g, ref) <= RMS_TOL
+    port, _ = pvref.port_std_process_batch(x[None], 1024, 4, ord("p"), 2.0)
+    assert_hop_parity(g, ref, port[0], pv.outHopSize, what=f"n={n}")
 
 
 def test_fused_odd_output_stride_and_offset_input(cuda):

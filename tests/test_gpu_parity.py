@@ -4,6 +4,7 @@ import pytest
 
 import pvref
 from pvamd import PhaseVocoder, REF_COMPAT, STANDARD, TIME_SHIFT, PITCH_SHIFT
+from signals import assert_hop_parity
 
 pytestmark = pytest.mark.gpu
 
@@ -64,6 +65,8 @@ def test_std_process_parity(cuda, effect, scale):
     assert g.shape == ref.shape
     err = rms(g, ref)
     assert err <= RMS_TOL, f"rms {err}"
+    port, _ = pvref.port_std_process_batch(x[None], N, hop_div, ord(effect), scale)
+    assert_hop_parity(g, ref, port[0], pv.outHopSize, what=f"{effect} {scale}")
 
 
 def test_std_process_multichannel(cuda):
@@ -113,8 +116,11 @@ def test_split_path_without_spectrum_output(cuda, N, hop_div, effect, scale, pac
         assert np.array_equal(g.view(np.uint32), ph.view(np.uint32))
     ref, _ = pvref.std_process_batch(xs, N, hop_div, ord(effect), scale)
     g2 = out2.cpu().numpy()
+    port, _ = pvref.port_std_process_batch(xs, N, hop_div, ord(effect), scale)
+    ref64 = pvref.std_process_channels(xs, N, hop_div, ord(effect), scale)
     for c in range(C):
         assert g2[c].shape == ref[c].shape and rms(g2[c], ref[c]) <= RMS_TOL, f"ch{c}"
+        assert_hop_parity(g2[c], ref64[c], port[c], pv.outHopSize, what=f"ch{c}")
 
 
 def pv_frames(n, hop):
@@ -274,6 +280,8 @@ def test_std_process_parity_geometries(cuda, N, hop_div, effect, scale):
     ref = pvref.std_process(x, N, hop_div, ord(effect), scale)
     assert out.shape[1] == ref.shape[0]
     assert rms(out.cpu().numpy()[0], ref) <= RMS_TOL
+    port, _ = pvref.port_std_process_batch(x[None], N, hop_div, ord(effect), scale)
+    assert_hop_parity(out.cpu().numpy()[0], ref, port[0], pv.outHopSize, what=f"{N}/{hop_div} {effect} {scale}")
 
 
 @pytest.mark.parametrize("C", [1, 32])
@@ -289,8 +297,11 @@ def test_long_streams_segmented_carry(cuda, C):
     out, _ = pv.process(to_dev(xs))
     g = out.cpu().numpy()
     ref, _ = pvref.std_process_batch(xs, N, hop_div, ord("t"), 0.5)
+    port, _ = pvref.port_std_process_batch(xs, N, hop_div, ord("t"), 0.5)
+    ref64 = pvref.std_process_channels(xs, N, hop_div, ord("t"), 0.5)
     for c in range(C):
         assert rms(g[c], ref[c]) <= RMS_TOL, f"C={C} ch{c}"
+        assert_hop_parity(g[c], ref64[c], port[c], pv.outHopSize, what=f"C={C} ch{c}")
 
 
 @pytest.mark.parametrize("mode", [STANDARD, REF_COMPAT])
@@ -328,8 +339,11 @@ def test_run_length_geometries(cuda, monkeypatch, F, effect, scale):
     out, _ = pv.process(to_dev(xs))
     g = out.cpu().numpy()
     ref, _ = pvref.std_process_batch(xs, N, hop_div, ord(effect), scale)
+    port, _ = pvref.port_std_process_batch(xs, N, hop_div, ord(effect), scale)
+    ref64 = pvref.std_process_channels(xs, N, hop_div, ord(effect), scale)
     for c in range(C):
         assert rms(g[c], ref[c]) <= RMS_TOL, f"F={F} ch{c}"
+        assert_hop_parity(g[c], ref64[c], port[c], pv.outHopSize, what=f"F={F} ch{c}")
     monkeypatch.setenv("PV_RUN_FRAMES", "16")
     pv16 = PhaseVocoder(N, effect, scale, hop_div, mode=STANDARD, max_channels=C, max_frames=440)
     out16, _ = pv16.process(to_dev(xs))

@@ -8,6 +8,7 @@ import pytest
 
 import pvref
 from pvamd import PITCH_SHIFT, REF_COMPAT, STANDARD, TIME_SHIFT, PhaseVocoder
+from signals import assert_hop_parity
 from test_gpu_parity import RMS_TOL, rms, synth
 
 pytestmark = pytest.mark.gpu
@@ -42,6 +43,10 @@ def test_random_configuration_matches_oracle(cuda, seed):
     out, spec = pv.process(torch.from_numpy(xs).cuda())
     g = out.cpu().numpy()
     frames = pv.num_frames(n)
+    if compat:
+        port, _ = pvref.port_compat_process_batch(xs, N, hop_div, out_hop=pv.outHopSize)
+    else:
+        port, _ = pvref.port_std_process_batch(xs, N, hop_div, ord(effect), scale)
     for c in range(C):
         if compat:
             ref = pvref.compat_process(xs[c], N, hop_div, out_hop=pv.outHopSize)
@@ -50,6 +55,9 @@ def test_random_configuration_matches_oracle(cuda, seed):
         assert g[c].shape == ref.shape, (seed, N, hop_div, effect, scale)
         assert np.isfinite(g[c]).all()
         assert rms(g[c], ref) <= RMS_TOL, (seed, N, hop_div, effect, scale, C, n)
+        if frames > 0:
+            assert_hop_parity(g[c], ref, port[c], pv.outHopSize,
+                              what=f"seed {seed} {'compat ' if compat else ''}{N}/{hop_div} {effect} {scale} ch{c} n={n}")
     if not compat and frames > 0:
         s = pv.unpack_spec(spec).cpu().numpy()
         _, ph = pvref.std_analysis(xs[0], N, hop, frames)

@@ -7,6 +7,7 @@ import pytest
 
 import pvref
 from pvamd import PITCH_SHIFT, STANDARD, TIME_SHIFT, PhaseVocoder, RealTimeVocoder
+from signals import assert_hop_parity
 
 pytestmark = pytest.mark.gpu
 
@@ -68,6 +69,8 @@ def test_rt_stream_matches_oracle(cuda, N, hop_div, effect, scale, per_push):
     xp, ref = oracle_stream(x, N, hop_div, effect, scale, K)
     err = rms(g, ref[:K * hs])
     assert err <= RMS_TOL, f"rms {err}"
+    port, _ = pvref.port_std_process_batch(xp[None], N, hop_div, ord(effect), scale, frames=K)
+    assert_hop_parity(g, ref[:K * hs], port[0, :K * hs], hs, what=f"rt {N}/{hop_div} {effect} {scale}")
     _, ph = pvref.std_analysis(xp, N, hop, K)
     gph = np.concatenate(phases)
     assert np.array_equal(gph.view(np.uint32), ph.view(np.uint32)), \
