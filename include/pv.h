@@ -47,6 +47,10 @@
  *   PV_FUSED_HALF=0      pitch 2 single launch: the MODE 3 gather and full-size inverse FFT
  *                        instead of the half-size resynthesis of X^2/|X| (MODE 4)
  *   PV_FUSED_BALANCE=0   single launch of one channel: uniform runs (no balanced F+1 runs)
+ *   PV_RESIDENT=0|1      pv_process(spec = NULL) of a plain STANDARD stretch at N = 1024, hop
+ *                        N/4, out hop 128: 0 never takes the channel-resident launch, 1 takes
+ *                        it at any channel count; unset: from pv_resident_min_channels up
+ *                        to 1024 channels (same output bits either way)
  *   PV_COMPAT_ANA_FRAMES=F  REF_COMPAT analysis run length (1..256, default 4)
  *   PV_RT_LAUNCH=direct  pv_rt_callback launches the kernel instead of replaying the graph
  *
@@ -82,7 +86,8 @@ extern "C" {
                                 pv_rt_pitch_push, pv_pitch_set_formant / pv_pitch_get_formant,
                                 pv_varresampler_* / pv_varresample / pv_varresample_steps /
                                 pv_varresample_length, pv_pitchmap_plan / pv_pitchmap_set /
-                                pv_pitchmap_output_length / pv_pitchmap_process) */
+                                pv_pitchmap_output_length / pv_pitchmap_process,
+                                pv_resident_min_channels) */
 
 typedef struct pv_handle pv_handle;
 
@@ -265,6 +270,16 @@ pv_status pv_segment_resynthesis(pv_handle* h, const pv_float2* spec, long long 
  * pv_pitch_set_formant is on).  Not
  * capturable itself (it allocates). */
 pv_status pv_reserve_spectrum(pv_handle* h);
+
+/* The channel-resident launch: pv_process(spec = NULL) with at least this many channels, on a
+ * handle with phase locking, formant preservation, the envelope warp and the transient reset
+ * off and x / out rows that are 8-byte aligned with even strides, runs one workgroup per
+ * channel that keeps the spectrum rows on chip — the split path's output bits, no spectrum rows
+ * (nothing is allocated, so such a call can be captured without pv_reserve_spectrum).  With
+ * PV_RESIDENT unset the choice also ends at 1024 channels, one round of the kernel on the chip
+ * (more take the split path); PV_RESIDENT=1 has no upper end.  0: this handle never takes it
+ * (geometry or PV_RESIDENT=0); pv_info.single_launch stays 0 either way. */
+int pv_resident_min_channels(const pv_handle* h);
 
 pv_status pv_process(pv_handle* h, const float* x, long long ldx, long long n_samples,
                      int channels, int frames, pv_float2* spec, long long ld_spec, float* out,

@@ -257,6 +257,8 @@ pv_status pv_get_info(const pv_handle* h, pv_info* info) {
     return PV_OK;
 }
 
+int pv_resident_min_channels(const pv_handle* h) { return h ? h->resident_min : 0; }
+
 #ifdef PV_FUSED_STAMPS
 // diagnostic build only (make variant NAME=stamps DEFS=-DPV_FUSED_STAMPS): the per-wave
 // phase stamps of the last k_fused launch, kFusedStampSlots per wave (scripts/fused_stamps.py)
@@ -346,6 +348,11 @@ pv_status pv_create(const pv_config* cfg, pv_handle** out) {
                     : 0;
     if (h->mode == PV_MODE_STANDARD && h->q == 1 && pv::fused_supported(h->L_syn, h->hs))
         h->F_fused = choose_fused_frames(h->F, work, h->hs, h->tail_len, h->env);
+    {
+        const ResidentGeometry rg{h->mode, h->pitch, h->L_ana, h->L_syn, h->hop, h->hs, h->q_pow2, h->k_lane,
+                                  h->F, h->tail_len, h->q};
+        h->resident_min = resident_min_channels(resident_supported(rg) && pv::resident_kernel(h->L_syn, h->hs), h->env);
+    }
 
     // ---- upload, workspace
     DeviceGuard g(cfg->device);

@@ -304,6 +304,41 @@ pv_status do_fused(pv_handle* h, const float* x, long long ldx, long long n, int
     return PV_OK;
 }
 
+// One workgroup per channel walks it from its first frame to its last (pv_resident.hip): the
+// rows stay in LDS, the decisions are made inline, the handle's F sets the seams.  The caller
+// has checked the handle (resident_min) and the alignment of x and out.
+pv_status do_resident(pv_handle* h, const float* x, long long ldx, long long n, int C, int frames, float* out,
+                      long long ldo, hipStream_t s) {
+    if (C == 0 || frames == 0) return PV_OK;
+    if (!x || !out) return fail(PV_ERR_ARG, "null x/out");
+    if (C > 1 && ldx < n) return fail(PV_ERR_ARG, "ldx < n_samples");
+    const long long olen = pv_output_length(h, frames);
+    if (C > 1 && ldo < olen) return fail(PV_ERR_ARG, "ldo < pv_output_length");
+    pv::ResidentParams p{};
+    p.x = x;
+    p.ldx = ldx;
+    p.n = n;
+    p.hop = h->hop;
+    p.frames = frames;
+    p.F = h->F;
+    p.win = h->d_win;
+    p.tw = h->d_tw_syn;    // the stage-major L-point table serves both directions
+    p.tws = h->d_tws_syn;  // e^{-2 pi i k/N}, k <= N/2: the analysis split's table too
+    p.ek = h->d_ek;
+    p.jk_mod = h->d_jk_mod;
+    p.rho = h->rho;
+    p.inv_q = h->inv_q;
+    p.p_mod = (unsigned)h->p_mod;
+    p.q = (unsigned)h->q;
+    p.gain = h->d_gain;
+    p.hs = h->hs;
+    p.out = out;
+    p.ldo = ldo;
+    p.out_len = olen;
+    PV_LAUNCH(h, KRD, s, pv::launch_resident(h->L_syn, C, p, s));
+    return PV_OK;
+}
+
 namespace {
 // the handle's own spectrum rows (split path, pv_process with spec = NULL): allocated and
 // zeroed once, under the handle's lock, so two threads' first calls allocate one buffer
@@ -384,6 +419,16 @@ pv_status process_impl(pv_handle* h, const float* x, long long ldx, long long n_
                        pv_float2* spec, long long ld_spec, float* out, long long ldo, hipStream_t s) {
     pv_status st = PV_OK;
     if (single_launch(h)) return do_fused(h, x, ldx, n_samples, channels, frames, spec, ld_spec, out, ldo, s);
+    // no spectrum output, a plain stretch the resident kernel serves, enough channels to fill the
+    // chip with one workgroup each, rows it can read and write two samples at a time: the rows
+    // stay on chip (no own-rows buffer: nothing is allocated)
+    // (the automatic choice stops at one round of the chip, kResidentRoundChannels: a second,
+    // partly filled round runs at one workgroup's latency)
+    const bool res_count = channels >= h->resident_min &&
+                           (h->env.resident == 1 || channels <= kResidentRoundChannels);
+    if (!spec && h->resident_min > 0 && res_count && !h->phase_lock && !h->formant &&
+        !h->pitch_formant && !h->transient && in_aligned(h, x, ldx) && out_aligned(out, ldo))
+        return do_resident(h, x, ldx, n_samples, channels, frames, out, ldo, s);
     // spec == NULL: the rows go through the handle's own buffer, and bins no output bin reads
     // (pitch > 1) are not analysed
     int src_hi = -1;

@@ -32,12 +32,13 @@ pv_status fail(pv_status s, const std::string& msg);
 
 // kernel ids of the per-launch profile and their names (pv_profile_read), index for index
 enum { KA, KRS, KC, KS, KSEAM, KCA, KRT, KF, KSL, KENV, KSF, KRES, KRTR, KSW, KON, KPK, KRST, KSR, KMS, KMC, KSM,
-       KVR, kNumKernels };
+       KVR, KRD, kNumKernels };
 inline constexpr const char* kKernelNames[] = {"analysis", "runsum", "carry", "synthesis", "seam",
                                                "compat_analysis", "rt", "fused", "synthesis_locked",
                                                "envelope", "synthesis_formant", "resample", "rt_resample",
                                                "synthesis_warp", "onset", "pick", "reset", "synthesis_reset",
-                                               "map_sum", "map_carry", "synthesis_map", "var_resample"};
+                                               "map_sum", "map_carry", "synthesis_map", "var_resample",
+                                               "resident"};
 static_assert(sizeof(kKernelNames) / sizeof(kKernelNames[0]) == kNumKernels, "one name per kernel id");
 
 // Move-only owner of one hipMalloc (Pinned: hipHostMalloc, device-mapped) allocation.  Converts
@@ -116,6 +117,7 @@ struct pv_handle {
     int N = 0, hop = 0, hs = 0, L_ana = 0, L_syn = 0, bins = 0, bins_pad = 0;
     int spec_bins = 0, spec_stride = 0, F = 16, tail_len = 0, max_runs = 0;
     int F_fused = 0;  // frames per run of the single-launch q = 1 path (0: not available)
+    int resident_min = 0;  // channels from which a spec = NULL call takes k_resident (0: never)
     pvtab::EnvOverrides env;  // environment overrides, read once by pv_create (pv.h lists them)
     int src_hi = 0;   // highest analysis bin any output bin reads (pitch map; L otherwise)
     int tables_ready = 1;  // 0: pv_config.tables_external until pv_import_tables
@@ -312,6 +314,10 @@ pv_status do_resynthesis(pv_handle* h, const pv_float2* spec, long long ld_spec,
                          const SegState* seg = nullptr, const float* env_from = nullptr);
 pv_status do_fused(pv_handle* h, const float* x, long long ldx, long long n, int C, int frames, pv_float2* spec,
                    long long ld_spec, float* out, long long ldo, hipStream_t s);
+// the channel-resident launch (pv_resident.hip) of a spec = NULL call: out equal to
+// do_analysis + do_resynthesis bit for bit, no spectrum rows anywhere
+pv_status do_resident(pv_handle* h, const float* x, long long ldx, long long n, int C, int frames, float* out,
+                      long long ldo, hipStream_t s);
 // pv_process after its checks (the caller holds the device guard and the profile call)
 pv_status process_impl(pv_handle* h, const float* x, long long ldx, long long n_samples, int channels, int frames,
                        pv_float2* spec, long long ld_spec, float* out, long long ldo, hipStream_t s);

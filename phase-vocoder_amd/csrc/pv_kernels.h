@@ -268,6 +268,25 @@ struct FusedParams {
 constexpr int kFusedStampSlots = 16;  // rt start, mt start, setup, frame 0..F-1, loop, end rt/mt, hw id
 #endif
 
+// channel-resident STANDARD time stretch (pv_resident.hip): one workgroup per channel, the
+// spectrum rows stay in LDS
+struct ResidentParams {
+    const float* x;
+    long long ldx, n;
+    int hop, frames, F;                // F: the handle's frames per run (the split path's seams)
+    const float* win;                  // analysis window (N)
+    const float2* tw;                  // stage-major twiddles, L-point (analysis = synthesis)
+    const float2* tws;                 // e^{-2 pi i k/N}, k <= L
+    const float* ek;                   // per-lane unwrap constants: e_k, (p j_k) mod q
+    const unsigned* jk_mod;
+    float rho, inv_q;
+    unsigned p_mod, q;                 // q a power of two <= 4096
+    const float* gain;                 // synthesis window * norm / N   (N)
+    int hs;                            // out hop
+    float* out;
+    long long ldo, out_len;
+};
+
 struct SeamParams {
     float* out;
     long long ldo, out_len;
@@ -380,6 +399,10 @@ bool synthesis_lane_kernel(int L, int mode, int hs, bool q_pow2, unsigned long l
 hipError_t launch_seam(int channels, const SeamParams& p, hipStream_t s);
 bool fused_supported(int L, int hs);
 hipError_t launch_fused(int L, int mode, int channels, const FusedParams& p, hipStream_t s);
+// the channel-resident kernel exists for this geometry (the host predicate
+// pvtab::resident_supported admits no other), and its launch
+bool resident_kernel(int L, int hs);
+hipError_t launch_resident(int L, int channels, const ResidentParams& p, hipStream_t s);
 size_t synthesis_lds_bytes(int L, int hs);
 hipError_t launch_fft(int n, int inverse, const float2* in, float2* out, const float2* tw, int batch,
                       hipStream_t s);

@@ -238,6 +238,9 @@ EnvOverrides read_env_overrides() {
     if (const char* ev = std::getenv("PV_FUSED_FRAMES")) e.fused_frames = std::atoi(ev);
     if (const char* en = std::getenv("PV_FUSED")) e.fused = (en[0] == '0') ? 0 : 1;
     if (const char* ev = std::getenv("PV_SYN_LANEK")) e.syn_lanek = (ev[0] == '0') ? 0 : 1;
+    // (anything but exactly "0" or "1" counts as unset)
+    if (const char* ev = std::getenv("PV_RESIDENT"))
+        e.resident = (ev[0] == '0' && ev[1] == 0) ? 0 : (ev[0] == '1' && ev[1] == 0) ? 1 : -1;
     return e;
 }
 
@@ -332,6 +335,17 @@ void fused_rounds(int frames, int F, bool balance, int* nwg, int* n4) {
             *n4 = (int)m;
         }
     }
+}
+
+bool resident_supported(const ResidentGeometry& g) {
+    return g.mode == PV_MODE_STANDARD && !g.pitch && g.L_ana == 512 && g.L_syn == 512 && g.hop == 256 &&
+           g.hs == 128 && g.q_pow2 && g.q >= 2 && g.q <= 4096 && g.k_lane &&
+           (long long)g.F * g.hs >= g.tail_len;
+}
+
+int resident_min_channels(bool supported, const EnvOverrides& env) {
+    if (!supported || env.resident == 0) return 0;
+    return env.resident == 1 ? 1 : kResidentAutoChannels;
 }
 
 // ---- resampler

@@ -72,6 +72,7 @@ struct EnvOverrides {
     int fused_half = 1, fused_balance = 1;     // PV_FUSED_HALF=0, PV_FUSED_BALANCE=0
     int run_frames = 0, fused_frames = 0;      // PV_RUN_FRAMES, PV_FUSED_FRAMES as given (0: unset)
     int fused = 1, syn_lanek = 1;              // PV_FUSED=0, PV_SYN_LANEK=0
+    int resident = -1;                         // PV_RESIDENT: 0 never, 1 whenever supported, -1 unset
 };
 EnvOverrides read_env_overrides();
 
@@ -86,6 +87,22 @@ int choose_run_frames(long long work, int L_syn, int L_ana, int mode, int wgs_pe
 int choose_fused_frames(int F, long long work, int hs, int tail_len, const EnvOverrides& env);
 // workgroups of the single launch and, when its rounds are balanced, the runs one frame longer
 void fused_rounds(int frames, int F, bool balance, int* nwg, int* n4);
+// The channel-resident kernel (pv_resident.hip) serves this handle geometry: a STANDARD time
+// stretch (no pitch map) at N = 1024, hop N/4, out hop 128, whose output-phase denominator q is
+// a power of two in [2, 4096] with per-lane unwrap constants, and whose runs cover the overlap.
+struct ResidentGeometry {
+    int mode, pitch, L_ana, L_syn, hop, hs, q_pow2, k_lane, F, tail_len;
+    unsigned long long q;
+};
+bool resident_supported(const ResidentGeometry& g);
+// the fewest channels from which pv_process(spec = NULL) takes the resident kernel on a
+// supported handle; 0: never.  Unset, PV_RESIDENT leaves the measured threshold
+// kResidentAutoChannels (profiles/resident_c3.txt).
+constexpr int kResidentAutoChannels = 1024;
+// one round of the kernel on the MI355X: 4 workgroups on each of 256 CUs.  Unset, PV_RESIDENT
+// takes the kernel for channel counts from the threshold up to this.
+constexpr int kResidentRoundChannels = 1024;
+int resident_min_channels(bool supported, const EnvOverrides& env);
 
 // ---- resampler presets (include/pv.h)
 double bessel_i0(double x);

@@ -18,6 +18,9 @@
 //       overrides apply, as in pv_create)
 //   tables_dump balance frames F
 //       prints "nwg n4": the single launch's workgroups and its runs one frame longer
+//   tables_dump resident mode pitch L_ana L_syn hop hs q_pow2 q k_lane F tail_len
+//       prints "supported threshold": resident_supported of the geometry and, with PV_RESIDENT
+//       from the environment, resident_min_channels
 // [file] absent or "-": stdout.
 #include <cstdint>
 #include <cstdio>
@@ -63,7 +66,8 @@ int usage() {
                  "       tables_dump resample P Q quality [file]\n"
                  "       tables_dump warp N hop out_hop [file]\n"
                  "       tables_dump choose C T N hop_div mode effect scale wgs_per_cu waves_per_wg\n"
-                 "       tables_dump balance frames F\n");
+                 "       tables_dump balance frames F\n"
+                 "       tables_dump resident mode pitch L_ana L_syn hop hs q_pow2 q k_lane F tail_len\n");
     return 2;
 }
 
@@ -183,6 +187,27 @@ int balance(int argc, char** argv) {
     return 0;
 }
 
+// resident mode pitch L_ana L_syn hop hs q_pow2 q k_lane F tail_len -> "supported threshold"
+// (PV_RESIDENT from the environment)
+int resident(int argc, char** argv) {
+    if (argc < 13) return usage();
+    ResidentGeometry g{};
+    g.mode = std::atoi(argv[2]);
+    g.pitch = std::atoi(argv[3]);
+    g.L_ana = std::atoi(argv[4]);
+    g.L_syn = std::atoi(argv[5]);
+    g.hop = std::atoi(argv[6]);
+    g.hs = std::atoi(argv[7]);
+    g.q_pow2 = std::atoi(argv[8]);
+    g.q = std::strtoull(argv[9], nullptr, 10);
+    g.k_lane = std::atoi(argv[10]);
+    g.F = std::atoi(argv[11]);
+    g.tail_len = std::atoi(argv[12]);
+    const bool ok = resident_supported(g);
+    std::printf("%d %d\n", ok ? 1 : 0, resident_min_channels(ok, read_env_overrides()));
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -192,5 +217,6 @@ int main(int argc, char** argv) {
     if (cmd == "warp") return dump_warp(argc, argv);
     if (cmd == "choose") return choose(argc, argv);
     if (cmd == "balance") return balance(argc, argv);
+    if (cmd == "resident") return resident(argc, argv);
     return dump_tables(argc, argv);
 }

@@ -130,6 +130,8 @@ def lib():
     L.pv_process.restype = i
     L.pv_reserve_spectrum.argtypes = [vp]
     L.pv_reserve_spectrum.restype = i
+    L.pv_resident_min_channels.argtypes = [vp]
+    L.pv_resident_min_channels.restype = i
     L.pv_set_phase_lock.argtypes = [vp, i]
     L.pv_set_phase_lock.restype = i
     L.pv_get_phase_lock.argtypes = [vp]

@@ -101,6 +101,8 @@ class PhaseVocoder:
         self.frames_per_run = info.frames_per_run
         self.lane_constants = info.lane_constants
         self.spec_layout = info.spec_layout
+        # channels from which process(spec=None) takes the channel-resident launch (0: never)
+        self.resident_min_channels = int(self._L.pv_resident_min_channels(self._h))
         if phase_lock:
             self.set_phase_lock(True)
         if formant:

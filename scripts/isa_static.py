@@ -30,6 +30,9 @@ FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off",
 KERNELS = {
     ("c3", "analysis"): ("pv_analysis.hip", ["-fno-slp-vectorize"], "_ZN2pv14k_std_analysisILi512ELb0ELi2ELb1E", 9),
     ("c3", "synthesis"): ("pv_kernels.hip", [], "_ZN2pv11k_synthesisILi512ELi0ELi1ELb1ELb1E", 17),
+    # the channel-resident launch (PV_RESIDENT): one kernel, two per-frame loops — the analysis
+    # waves' (no global store: its rows go to LDS) and the synthesis wave's (resident_loops)
+    ("c3", "resident"): ("pv_resident.hip", [], "_ZN2pv10k_residentILi512ELi1E", (9, 17)),
     # config 4 (bench.py: no spectrum handed back, pitch 1.5): the instantiation analysing
     # lane registers 0 .. 11 (bins < 768; 12 square roots, no bin L)
     ("c4", "analysis"): ("pv_analysis.hip", ["-fno-slp-vectorize"], "_ZN2pv14k_std_analysisILi1024ELb0ELi4ELb1ELi12E", 12),
@@ -145,6 +148,32 @@ def frame_loop(asm, prefix, trans_pf, extra):
     return best
 
 
+def resident_loops(asm, prefix, trans_pf, extra):
+    """k_resident's two frame loops: the synthesis wave's is frame_loop's (sines, cosines and
+    the output stores); the analysis waves' is the innermost loop with the frame's square roots
+    and no sine.  The analysis loop carries the bounds-checked input loads of the channel's last
+    frames beside the vector loads, so its count is an upper bound of the steady state."""
+    ana_pf, syn_pf = trans_pf
+    syn = frame_loop(asm, prefix, syn_pf, extra)
+
+    def count(seg, ops):
+        return sum(1 for o, _ in seg if o.startswith(ops))
+    cands = [(a, b, seg) for a, b, seg in loops_of(asm, prefix)
+             if count(seg, ("v_sqrt",)) >= ana_pf and count(seg, ("v_sin", "v_cos")) == 0]
+    inner = [c for c in cands if not any(o is not c and c[0] <= o[0] and o[1] <= c[1] for o in cands)]
+    if syn is None or not inner:
+        return None
+    ana = min(inner, key=lambda c: c[1] - c[0])[2]
+    a_cnt, a_cyc = price(ana, extra)
+    s_seg, s_fpl, s_cyc, s_cnt = syn
+    return {"symbol": prefix,
+            "analysis_loop": {"loop_instructions": len(ana), "frames_per_trip": 1, "counts_per_trip": dict(a_cnt),
+                              "valu_cycles_per_frame": round(a_cyc, 1)},
+            "synthesis_loop": {"loop_instructions": len(s_seg), "frames_per_trip": s_fpl,
+                               "counts_per_trip": dict(s_cnt), "valu_cycles_per_frame": round(s_cyc / s_fpl, 1)},
+            "valu_cycles_per_frame": round(a_cyc + s_cyc / s_fpl, 1)}
+
+
 def main():
     extra = {}
     p = os.path.join(ROOT, FAST_EXTRA)
@@ -172,6 +201,11 @@ def main():
                                                "frames_per_trip": 1, "scope": "whole kernel (loops counted once)",
                                                "counts_per_trip": dict(cnt),
                                                "valu_cycles_per_frame": round(cyc, 1)}
+                continue
+            if isinstance(trans_pf, tuple):
+                ent = resident_loops(asm, prefix, trans_pf, extra)
+                if ent is not None:
+                    out.setdefault(wl, {})[key] = ent
                 continue
             best = frame_loop(asm, prefix, trans_pf, extra)
             if best is None:
