@@ -304,7 +304,7 @@ void pvr_split_c32(const pvr_c32* z, int L, const pvr_c32* tws, pvr_c32* X) {
         pvr_c32 w = tws[k];
         /* contract v2: the odd part's twiddle product accumulated onto the even part with
          * two fused operations per component (one rounding each), as the GPU's
-         * split_chunk / split_chunk_bp / real_split / bin_l_real */
+         * split_chunk_bp / bin_l_real */
         X[k].x = fmaf(orr, w.x, fmaf(-oi, w.y, er));
         X[k].y = fmaf(orr, w.y, fmaf(oi, w.x, ei));
     }

@@ -99,11 +99,7 @@ __device__ __forceinline__ void ana_run(const AnaParams& p, const AnaLds& lt, fl
     PV_FOR_BINS(E, lane, { phprev[i] = 0.0f; sacc[i] = Acc(0); })
     // mirrored-pair split (frame below): every bin analysed, L <= 512 (the L = 1024 kernels
     // sit at their VGPR bound)
-#ifdef PV_ANA_NOPAIR
-    constexpr bool PAIR = false;
-#else
     constexpr bool PAIR = (NA == E) && (L <= 512);
-#endif
     constexpr int H = E / 2;
     const int rev = ((64 - lane) & 63) << 2;            // lane reversal l -> (64 - l) mod 64
     const float2* baseT = twsl + lane;                  // split twiddles of the lane's bins
@@ -128,8 +124,7 @@ __device__ __forceinline__ void ana_run(const AnaParams& p, const AnaLds& lt, fl
 #else
             const float2 wv = lds_ld(&wl[64 * q]);  // window samples 2 (lane + 64 q) + {0,1}
 #endif
-            z[q].x = xr[q].x * wv.x;
-            z[q].y = xr[q].y * wv.y;
+            win_mul(xr[q], wv, z[q]);
         }
     };
     // NA < E (pv_process without a spectrum output, pitch > 1: the launcher's instantiation
@@ -328,19 +323,9 @@ __device__ __forceinline__ void ana_run(const AnaParams& p, const AnaLds& lt, fl
         });
         wave_lds_sync();  // tile reads done before the next frame's pass_store
     };
-    auto load_fast = [&](int u, float2 (&xr)[E]) {
-        const float* src = xc + (long long)(t0 + u) * p.hop;
-#pragma unroll
-        for (int q = 0; q < E; ++q) xr[q] = *reinterpret_cast<const float2*>(src + 2 * (lane + 64 * q));
-    };
+    auto load_fast = [&](int u, float2 (&xr)[E]) { frame_load_vec<E>(xc, (long long)(t0 + u) * p.hop, lane, xr); };
     auto load_checked = [&](int u, float2 (&xr)[E]) {
-        const long long base = (long long)(t0 + u) * p.hop;
-#pragma unroll
-        for (int q = 0; q < E; ++q) {
-            const long long s = base + 2 * (lane + 64 * q);
-            xr[q].x = (s < p.n) ? xc[s] : 0.0f;
-            xr[q].y = (s + 1 < p.n) ? xc[s + 1] : 0.0f;
-        }
+        frame_load_checked<E>(xc, (long long)(t0 + u) * p.hop, p.n, lane, xr);
     };
     // frames whose N samples are all inside [0, n) take the vector-load path; the (at most
     // N/hop) frames at the end of a channel take the bounds-checked path.
@@ -365,7 +350,6 @@ __device__ __forceinline__ void ana_run(const AnaParams& p, const AnaLds& lt, fl
             auto src = [&](int u) { return xc + (long long)(t0 + min(u, ufast - 1)) * p.hop + 2 * lane; };
 #endif
             int u = 0;
-#ifndef PV_ANA_NOROT
             // Register rotation: frames are walked in groups of RR = E / D, after which the
             // window has moved by E registers.  Frame u + r (r < RR) holds its pair q in
             // register (q + D r) mod E, so its D new pairs land in the registers frame u + r - 1
@@ -390,9 +374,7 @@ __device__ __forceinline__ void ana_run(const AnaParams& p, const AnaLds& lt, fl
 #else
                         const float2 wv = lds_ld(&wl[64 * q]);
 #endif
-                        const float2 s = xr[(q + D * r) % E];
-                        z[q].x = s.x * wv.x;
-                        z[q].y = s.y * wv.y;
+                        win_mul(xr[(q + D * r) % E], wv, z[q]);
                     }
                 };
                 for (; u < umain; u += RR) {
@@ -408,7 +390,6 @@ __device__ __forceinline__ void ana_run(const AnaParams& p, const AnaLds& lt, fl
                     });
                 }
             }
-#endif
             auto consume = [&](const f2v (&xv)[D]) {
 #pragma unroll
                 for (int q = 0; q < E - D; ++q) xr[q] = xr[q + D];

@@ -169,13 +169,7 @@ __global__ __launch_bounds__(256) void k_compat_analysis(AnaParams p) {
         wave_lds_sync();  // tile reads done before the next frame's pass_store
     };
     auto load_checked = [&](int u, float2 (&xs)[E / 2]) {
-        const long long base = (long long)(t0 + u) * p.hop;
-#pragma unroll
-        for (int m = 0; m < E / 2; ++m) {
-            const long long sidx = base + 2 * (lane + 64 * m);
-            xs[m].x = (sidx < p.n) ? xc[sidx] : 0.0f;
-            xs[m].y = (sidx + 1 < p.n) ? xc[sidx + 1] : 0.0f;
-        }
+        frame_load_checked<E / 2>(xc, (long long)(t0 + u) * p.hop, p.n, lane, xs);
     };
     // frames whose N samples lie inside [0, n) (and 8-byte aligned) take vector loads
     const long long lastfull = (p.aligned && p.n >= N) ? (p.n - N) / p.hop : -1;
@@ -235,88 +229,97 @@ template <int L>
 static size_t ana_lds_compat() {
     return sizeof(float2) * (ana_twl_n<L>() + (L + 2) + 4 * Geo<L>::TILE) + sizeof(float) * L;
 }
-// twiddles + 4 tiles + 4 rings (tails) [+ gain] + ek/jk + pitch map; with register
-// overlap-add at L <= 512 the gains live in registers and gainl is not allocated
-
-#define PV_DISPATCH_L(L_, ...)                        \
+// the statement(s) with LL = L as a constant; an L without kernels returns DEFAULT_
+#define PV_DISPATCH_L(L_, DEFAULT_, ...)              \
     switch (L_) {                                     \
         case 128: { constexpr int LL = 128; __VA_ARGS__; } break;   \
         case 256: { constexpr int LL = 256; __VA_ARGS__; } break;   \
         case 512: { constexpr int LL = 512; __VA_ARGS__; } break;   \
         case 1024: { constexpr int LL = 1024; __VA_ARGS__; } break; \
         case 2048: { constexpr int LL = 2048; __VA_ARGS__; } break; \
-        default: return hipErrorInvalidValue;         \
-    }
+    }                                                 \
+    return DEFAULT_
 
+// The k_std_analysis instantiation of a geometry, its waves per workgroup and its LDS bytes.
+// d: hop / 128 when the input is aligned and the hop a multiple of 128, else 0 — the
+// shifted-register input needs d in {1, 2, 4}, d < E and per-lane e_k.  src_hi: the highest bin
+// read afterwards; below L (config 4, pitch 1.5: bins 684 .. 1024 unread) the L = 1024 packed
+// hop-512 kernel analyses only the lane registers that hold a read bin, in whole chunks of
+// kAnaChunk.
+struct StdAnaKernel {
+    void (*kern)(AnaParams);  // nullptr: no kernel for this L
+    int waves;
+    size_t lds;
+};
+template <int LL, bool PK>
+static StdAnaKernel std_analysis_full(int d, bool ek_lane) {
+    constexpr int E_ = LL / 64;  // D < E (instantiated for every L, chosen for the checked ones)
+    constexpr int D1 = (1 < E_) ? 1 : 0, D2 = (2 < E_) ? 2 : 0, D4 = (4 < E_) ? 4 : 0;
+    const size_t lds = ana_lds_std<LL>(!ek_lane);
+    if (ek_lane && LL >= 256 && LL <= 1024 && (d == 1 || d == 2 || d == 4) && d < E_) {
+        if (d == 1) return {k_std_analysis<LL, false, D1, PK>, kAnaWG, lds};
+        if (d == 2) return {k_std_analysis<LL, false, D2, PK>, kAnaWG, lds};
+        return {k_std_analysis<LL, false, D4, PK>, kAnaWG, lds};
+    }
+    if (ek_lane) return {k_std_analysis<LL, false, 0, PK>, kAnaWG, lds};
+    return {k_std_analysis<LL, true, 0, PK>, kAnaWG, lds};
+}
+// the hop-512 kernel that analyses na < E lane registers: L = 1024 with packed rows (the other
+// instantiations exist but are not chosen)
+template <int LL, bool PK>
+static StdAnaKernel std_analysis_partial(int na, const StdAnaKernel& full) {
+    constexpr int E_ = LL / 64, D4 = (4 < E_) ? 4 : 0;
+    if (LL != 1024 || !PK) return full;
+    if (na <= 8) return {k_std_analysis<LL, false, D4, PK, (8 < E_ ? 8 : E_)>, full.waves, full.lds};
+    if (na <= 10) return {k_std_analysis<LL, false, D4, PK, (10 < E_ ? 10 : E_)>, full.waves, full.lds};
+    if (na <= 12) return {k_std_analysis<LL, false, D4, PK, (12 < E_ ? 12 : E_)>, full.waves, full.lds};
+    if (na <= 14) return {k_std_analysis<LL, false, D4, PK, (14 < E_ ? 14 : E_)>, full.waves, full.lds};
+    return full;
+}
 template <bool PK>
-static hipError_t launch_std_analysis_t(int L, dim3 grid, const AnaParams& p, hipStream_t s) {
-    PV_DISPATCH_L(L, {
-        // shifted-register input when hop = 128 D (D < E)
-        const int d = (p.aligned && p.hop % 128 == 0) ? p.hop / 128 : 0;
-        if (p.ek_lane && LL >= 256 && LL <= 1024 && (d == 1 || d == 2 || d == 4) && d < LL / 64) {
-            constexpr int E_ = LL / 64;  // D < E (instantiated for every L, run for the checked ones)
-            constexpr int D1 = (1 < E_) ? 1 : 0, D2 = (2 < E_) ? 2 : 0, D4 = (4 < E_) ? 4 : 0;
-            const size_t lds = ana_lds_std<LL>(false);
-            auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(64 * kAnaWG), lds, s, p); };
-            if (d == 1) go(k_std_analysis<LL, false, D1, PK>);
-            else if (d == 2) go(k_std_analysis<LL, false, D2, PK>);
-            else if (LL == 1024 && PK && p.src_hi < LL) {
-                // bins above src_hi unread (config 4, pitch 1.5: 684 .. 1024): the registers
-                // analysed, in whole chunks of kAnaChunk
-                const int na = kAnaChunk * ((p.src_hi + 64 * kAnaChunk) / (64 * kAnaChunk));
-                if (na <= 8) go(k_std_analysis<LL, false, D4, PK, (8 < E_ ? 8 : E_)>);
-                else if (na <= 10) go(k_std_analysis<LL, false, D4, PK, (10 < E_ ? 10 : E_)>);
-                else if (na <= 12) go(k_std_analysis<LL, false, D4, PK, (12 < E_ ? 12 : E_)>);
-                else if (na <= 14) go(k_std_analysis<LL, false, D4, PK, (14 < E_ ? 14 : E_)>);
-                else go(k_std_analysis<LL, false, D4, PK>);
-            } else go(k_std_analysis<LL, false, D4, PK>);
-        } else if (p.ek_lane) hipLaunchKernelGGL((k_std_analysis<LL, false, 0, PK>), grid, dim3(256), ana_lds_std<LL>(false), s, p);
-        else hipLaunchKernelGGL((k_std_analysis<LL, true, 0, PK>), grid, dim3(256), ana_lds_std<LL>(true), s, p);
-    });
-    return hipGetLastError();
+static StdAnaKernel std_analysis_full_t(int L, int d, bool ek_lane) {
+    PV_DISPATCH_L(L, (StdAnaKernel{nullptr, kAnaWG, 0}), return (std_analysis_full<LL, PK>(d, ek_lane)));
+}
+template <bool PK>
+static StdAnaKernel std_analysis_partial_t(int L, int na, const StdAnaKernel& full) {
+    PV_DISPATCH_L(L, full, return (std_analysis_partial<LL, PK>(na, full)));
+}
+static StdAnaKernel std_analysis_kernel(int L, int d, bool ek_lane, bool packed, int src_hi) {
+    const StdAnaKernel full = packed ? std_analysis_full_t<true>(L, d, ek_lane) : std_analysis_full_t<false>(L, d, ek_lane);
+    if (!(ek_lane && d == 4 && src_hi < L)) return full;
+    const int na = kAnaChunk * ((src_hi + 64 * kAnaChunk) / (64 * kAnaChunk));
+    return packed ? std_analysis_partial_t<true>(L, na, full) : std_analysis_partial_t<false>(L, na, full);
 }
 
 // workgroups of the STANDARD analysis kernel launch_std_analysis picks for an aligned input
-// (hop = 128 d when that divides) that one CU holds at once (0 if the runtime cannot say),
-// and its waves per workgroup
-template <bool PK>
-static int std_analysis_wgs_per_cu_t(int L, int hop, bool ek_lane, int* waves_per_wg) {
-    int n = 0;
-    *waves_per_wg = 4;
-    if (L != 128 && L != 256 && L != 512 && L != 1024 && L != 2048) return 0;
-        auto occ = [&](const void* k, int W, size_t lds) {
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k, 64 * W, lds) != hipSuccess) n = 0;
-        *waves_per_wg = W;
-    };
-    PV_DISPATCH_L(L, {
-        const int d = (hop % 128 == 0) ? hop / 128 : 0;
-        if (ek_lane && LL >= 256 && LL <= 1024 && (d == 1 || d == 2 || d == 4) && d < LL / 64) {
-            constexpr int E_ = LL / 64;
-            constexpr int D1 = (1 < E_) ? 1 : 0, D2 = (2 < E_) ? 2 : 0, D4 = (4 < E_) ? 4 : 0;
-            if (d == 1) occ((const void*)k_std_analysis<LL, false, D1, PK>, kAnaWG, ana_lds_std<LL>(false));
-            else if (d == 2) occ((const void*)k_std_analysis<LL, false, D2, PK>, kAnaWG, ana_lds_std<LL>(false));
-            else occ((const void*)k_std_analysis<LL, false, D4, PK>, kAnaWG, ana_lds_std<LL>(false));
-        } else if (ek_lane) occ((const void*)k_std_analysis<LL, false, 0, PK>, 4, ana_lds_std<LL>(false));
-        else occ((const void*)k_std_analysis<LL, true, 0, PK>, 4, ana_lds_std<LL>(true));
-    });
-    return n;
-}
+// that one CU holds at once (0 if the runtime cannot say), and its waves per workgroup.
+// src_hi = L: the handle asks at creation, before any call says whether a spectrum goes out, so
+// the answer is the full-row kernel's, as it always was.
 int std_analysis_wgs_per_cu(int L, int hop, bool ek_lane, bool packed, int* waves_per_wg) {
-    return packed ? std_analysis_wgs_per_cu_t<true>(L, hop, ek_lane, waves_per_wg)
-                  : std_analysis_wgs_per_cu_t<false>(L, hop, ek_lane, waves_per_wg);
+    const StdAnaKernel k = std_analysis_kernel(L, (hop % 128 == 0) ? hop / 128 : 0, ek_lane, packed, L);
+    *waves_per_wg = k.waves;
+    int n = 0;
+    if (k.kern == nullptr ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)k.kern, 64 * k.waves, k.lds) != hipSuccess)
+        n = 0;
+    return n;
 }
 
 hipError_t launch_std_analysis(int L, int channels, const AnaParams& p, hipStream_t s) {
     const dim3 grid((p.nruns + 3) / 4, channels);
-    return p.packed ? launch_std_analysis_t<true>(L, grid, p, s) : launch_std_analysis_t<false>(L, grid, p, s);
+    const int d = (p.aligned && p.hop % 128 == 0) ? p.hop / 128 : 0;
+    const StdAnaKernel k = std_analysis_kernel(L, d, p.ek_lane != 0, p.packed != 0, p.src_hi);
+    if (k.kern == nullptr) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k.kern, grid, dim3(64 * k.waves), k.lds, s, p);
+    return hipGetLastError();
 }
 
 hipError_t launch_compat_analysis(int L, int channels, const AnaParams& p, hipStream_t s) {
     dim3 grid((p.nruns + 3) / 4, channels);
-    PV_DISPATCH_L(L, {
+    PV_DISPATCH_L(L, hipErrorInvalidValue, {
         hipLaunchKernelGGL(k_compat_analysis<LL>, grid, dim3(256), ana_lds_compat<LL>(), s, p);
+        return hipGetLastError();
     });
-    return hipGetLastError();
 }
 
 

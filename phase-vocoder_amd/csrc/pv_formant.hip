@@ -107,7 +107,7 @@ __global__ __launch_bounds__(256, (L <= 256) ? 4 : (L == 512) ? 3 : 2) void k_en
                                 min(n1, N - n1) <= order ? z[idx].y * inv_n : 0.0f);
         });
         fft_run<L, false, true, 0, 0, V3X>(v, tile, twl, tw0, lane);
-        // real part of the real split (real_split's operations), bins lane + 64 i and L
+        // real part of the real split (split_chunk_bp's operations), bins lane + 64 i and L
         float2 A[E + 1], Bz[E + 1], tw[E + 1];
 #pragma unroll
         for (int i = 0; i <= E; ++i) {

@@ -1,7 +1,8 @@
-// pv_frame.hpp — per-frame building blocks shared by the batched kernels (pv_kernels.hip)
-// and the real-time kernel (pv_rt.hip): the real-FFT split of the analysis transform and
-// the whole synthesis of one frame (phase propagation -> polar->rect -> C2R pre-split ->
-// inverse FFT).
+// pv_frame.hpp — per-frame building blocks shared by the batched kernels (pv_kernels.hip,
+// pv_analysis.hip), the single-launch kernels (pv_fused.hip, pv_resident.hip) and the real-time
+// kernel (pv_rt.hip): the frame input load and window, the real-FFT split of the analysis
+// transform and its polar step, the whole synthesis of one frame (phase propagation ->
+// polar->rect -> C2R pre-split -> inverse FFT) and the register overlap-add.
 #pragma once
 #include "pv_device.hpp"
 #include "pv_lock.hpp"
@@ -12,70 +13,6 @@
 
 
 namespace pv {
-
-// Real-FFT split of bin k (0 <= k <= L) from the natural-order L-point transform in tile.
-template <int L>
-__device__ __forceinline__ float2 real_split(const float2* tile, const float2* __restrict__ tws, int k) {
-    using G_ = Geo<L>;
-    const float2 A = tile[G_::pad(k & (L - 1))];
-    const float2 Bz = tile[G_::pad((L - k) & (L - 1))];
-    const float er = 0.5f * (A.x + Bz.x);
-    const float ei = 0.5f * (A.y - Bz.y);
-    const float orr = 0.5f * (A.y + Bz.y);
-    const float oi = 0.5f * (Bz.x - A.x);
-    const float2 tw = tws[k];
-    float Xr = __builtin_fmaf(orr, tw.x, __builtin_fmaf(-oi, tw.y, er));  // contract v2
-    float Xi = __builtin_fmaf(orr, tw.y, __builtin_fmaf(oi, tw.x, ei));
-    if (k == 0 || k == L) Xi = 0.0f;
-    return make_float2(Xr, Xi);
-}
-
-// Bins i0 .. i0+CH-1 of a lane (reads batched; entries past E are dummies).
-// TWICE: X is returned scaled by exactly 2 (the four halvings dropped).  Scaling by a
-// power of two commutes with every rounding here, so 2X is bit-exactly twice the
-// contract's X and atan2 of it is the contract's phase bit for bit (a = min/max and the
-// sign tests are scale-free); the caller halves the magnitude.  (Outside the denormal range:
-// where a halved sum of the contract is an fp32 denormal it rounds and the doubled one does
-// not, so bins of |X| < 2^-62 can differ from the contract in the last place — DESIGN.md §3.2.)
-template <int L, int CH, bool TWICE = false>
-__device__ __forceinline__ void split_chunk(const float2* tile, const float2* twsl, int lane, int i0,
-                                            float2 (&X)[CH]) {
-    using G_ = Geo<L>;
-    constexpr int E = G_::E;
-    // A = Z[k], B = Z[(L-k) mod L], k = lane + 64 i: affine in i from two per-lane bases;
-    // only (lane 0, i = 0) wraps (B = Z[0]) and bin L (i = E, lane 0) uses Z[0] twice.
-    const float2* baseA = tile + G_::pad(lane);
-    const float2* baseB = tile + G_::pad(L - lane);
-    const float2* baseT = twsl + lane;
-    float2 A[CH], Bz[CH], tw[CH];
-#pragma unroll
-    for (int c = 0; c < CH; ++c) {
-        const int i = i0 + c;
-        if (i < E) {
-            A[c] = lds_ld(&baseA[G_::padc(64 * i)]);
-            Bz[c] = lds_ld((i == 0 && lane == 0) ? tile : &baseB[-G_::padc(64 * i)]);
-            tw[c] = lds_ld(&baseT[64 * i]);
-        } else {
-            A[c] = lds_ld(tile);
-            Bz[c] = A[c];
-            tw[c] = lds_ld(&twsl[L]);
-        }
-    }
-    // (scalar form: a packed-instruction split measured slower, latency-bound chains)
-#pragma unroll
-    for (int c = 0; c < CH; ++c) {
-        const int i = i0 + c;
-        constexpr float h = TWICE ? 1.0f : 0.5f;
-        const float er = h * (A[c].x + Bz[c].x);
-        const float ei = h * (A[c].y - Bz[c].y);
-        const float orr = h * (A[c].y + Bz[c].y);
-        const float oi = h * (Bz[c].x - A[c].x);
-        float Xr = __builtin_fmaf(orr, tw[c].x, __builtin_fmaf(-oi, tw[c].y, er));  // contract v2
-        float Xi = __builtin_fmaf(orr, tw[c].y, __builtin_fmaf(oi, tw[c].x, ei));
-        if (i >= E || (i == 0 && lane == 0)) Xi = 0.0f;  // bins 0 and L are real
-        X[c] = make_float2(Xr, Xi);
-    }
-}
 
 // register index holding slot c after the last FFT pass (inverse of last_slot)
 template <int L>
@@ -91,14 +28,58 @@ constexpr int slot_reg(int c) {
 template <int E, bool PACKED>
 constexpr int bin_at(int pos) { return !PACKED ? pos : pos == 0 ? 0 : pos == 1 ? E : pos - 1; }
 
-// split_chunk from the last FFT pass's registers instead of the natural-order image in LDS
-// (no final tile store, no tile reads): lane l holds Z[l + 64 c] in register slot_reg(c), so
+// The frame's input samples in registers: xr[q] = samples base + 2 (lane + 64 q) + {0, 1},
+// registers FIRST .. E-1 (FIRST > 0: a shifted-register input loads only its new pairs).
+// frame_load_vec: 8-byte loads, for a frame wholly inside [0, n) of an aligned channel;
+// frame_load_checked: every sample against n, zeros past it.
+template <int E, int FIRST = 0>
+__device__ __forceinline__ void frame_load_vec(const float* xc, long long base, int lane, float2 (&xr)[E]) {
+#pragma unroll
+    for (int q = FIRST; q < E; ++q) xr[q] = *reinterpret_cast<const float2*>(xc + base + 2 * (lane + 64 * q));
+}
+template <int E, int FIRST = 0>
+__device__ __forceinline__ void frame_load_checked(const float* xc, long long base, long long n, int lane,
+                                                   float2 (&xr)[E]) {
+#pragma unroll
+    for (int q = FIRST; q < E; ++q) {
+        const long long s = base + 2 * (lane + 64 * q);
+        xr[q].x = (s < n) ? xc[s] : 0.0f;
+        xr[q].y = (s + 1 < n) ? xc[s + 1] : 0.0f;
+    }
+}
+// frame t of a channel: vector loads up to frame `lastfull` (the last one wholly inside, -1
+// when none is or the channel is not aligned), the bounds-checked loads after it.  (The test
+// stays in here: handed in as a flag it flips the branch sense in the callers' assembly.)
+template <int E, int FIRST = 0>
+__device__ __forceinline__ void load_frame(const float* xc, int t, int hop, long long n, long long lastfull,
+                                           int lane, float2 (&xr)[E]) {
+    const long long base = (long long)t * hop;
+    if (t <= lastfull) frame_load_vec<E, FIRST>(xc, base, lane, xr);
+    else frame_load_checked<E, FIRST>(xc, base, n, lane, xr);
+}
+
+// Window multiply of one register: the samples 2 (lane + 64 q) + {0, 1} times their window
+// samples (from LDS or held in registers), two plain products.  The loop over q stays with the
+// caller: written in here it moves the loop variable's stack slot in the caller's frame, and
+// that alone reorders k_fused's and k_resident's instructions (scripts/asm_diff.py).
+__device__ __forceinline__ void win_mul(const float2& x, const float2& w, float2& z) {
+    z.x = x.x * w.x;
+    z.y = x.y * w.y;
+}
+
+// Real split of a chunk of bins from the last FFT pass's registers (no final tile store, no
+// tile reads): lane l holds Z[l + 64 c] in register slot_reg(c), so
 // A = Z[k], k = l + 64 i, is the lane's own register and B = Z[(L - k) mod L] =
 // Z[(64 - l) + 64 (E - 1 - i)] is register slot E-1-i of lane 64 - l — a lane reversal by
 // ds_bpermute (crossbar only).  Lane 0's partners are its own registers (Z[(L - 64 i) mod L]
-// = slot (E - i) mod E): its permute reads itself and lane0_mov2 then puts them in.  Same
-// operands, same operations as split_chunk: bit-identical bins.  Chunk positions P0 ..
-// P0 + CH - 1 are bins bin_at<E, PACKED>(position) (positions past E are dummies).
+// = slot (E - i) mod E): its permute reads itself and lane0_mov2 then puts them in.  Chunk
+// positions P0 .. P0 + CH - 1 are bins bin_at<E, PACKED>(position) (positions past E are dummies).
+// TWICE: X is returned scaled by exactly 2 (the four halvings dropped).  Scaling by a
+// power of two commutes with every rounding here, so 2X is bit-exactly twice the
+// contract's X and atan2 of it is the contract's phase bit for bit (a = min/max and the
+// sign tests are scale-free); the caller halves the magnitude.  (Outside the denormal range:
+// where a halved sum of the contract is an fp32 denormal it rounds and the doubled one does
+// not, so bins of |X| < 2^-62 can differ from the contract in the last place — DESIGN.md §3.2.)
 template <int L, int CH, bool TWICE, int P0, bool PACKED = false>
 __device__ __forceinline__ void split_chunk_bp(const float2 (&v)[Geo<L>::E], const float2* twsl, int lane,
                                                float2 (&X)[CH]) {
@@ -113,11 +94,7 @@ __device__ __forceinline__ void split_chunk_bp(const float2 (&v)[Geo<L>::E], con
             A[c] = v[slot_reg<L>(i)];
             const float2 o = v[slot_reg<L>(E - 1 - i)];
             const float2 m = v[slot_reg<L>((E - i) & (E - 1))];
-#ifdef PV_LANE0_PRESEL
-            if constexpr (true) {
-#else
             if constexpr (L >= 1024) {
-#endif
                 // (the L = 1024 kernels sit at their 168-VGPR bound: m is selected before the
                 // permute rather than kept live across it, which spills there)
                 const bool l0 = lane == 0;
@@ -180,22 +157,52 @@ __device__ __forceinline__ void bin_l_real(const float2 (&v)[Geo<L>::E], const f
     phL = (Xr < 0.0f) ? kPi : 0.0f;
 }
 
-// bin_l_real from the natural-order image in LDS (the fused kernel's split reads the tile):
-// Z[0] = tile[0], the same address on every lane
-template <int L, bool TWICE>
-__device__ __forceinline__ void bin_l_real_tile(const float2* tile, const float2* twsl, float& magL, float& phL) {
-    const float2 z0 = lds_ld(tile);
-    const float ax = z0.x, ay = z0.y;
-    const float2 tw = lds_ld(&twsl[L]);
-    constexpr float h = TWICE ? 1.0f : 0.5f;
-    const float er = h * (ax + ax);
-    const float orr = h * (ay + ay);
-    const float oi = h * (ax - ax);
-    const float Xr = __builtin_fmaf(orr, tw.x, __builtin_fmaf(-oi, tw.y, er));  // contract v2
-    const float zero = 0.0f;
-    const float m = __builtin_amdgcn_sqrtf(__builtin_fmaf(Xr, Xr, zero * zero));
-    magL = TWICE ? 0.5f * m : m;
-    phL = (Xr < 0.0f) ? kPi : 0.0f;
+// {magnitude, contract phase} of a bin pair from its doubled split (split_chunk_bp TWICE): both
+// phases through the packed atan2 (bit-identical to atan2_pv per half), the magnitudes by the
+// hardware square root (<= 1 ulp: they only scale the output; the phase, which drives the
+// unwrap decisions, stays bit-exact), halved.  Each bin is handed to sink(IC<c>, mag, phase) as
+// soon as its magnitude exists, so a caller's row store keeps its place between the two square
+// roots (the kernels' schedules are sensitive to that order).
+template <typename Sink>
+__device__ __forceinline__ void polar_of_pair(const float2 (&X)[2], const Sink& sink) {
+    const f2v ph2 = atan2_pv2(X[0].y, X[0].x, X[1].y, X[1].x);
+    sink(IC<0>{}, half_sqrt(__builtin_fmaf(X[0].x, X[0].x, X[0].y * X[0].y)), ph2.x);
+    sink(IC<1>{}, half_sqrt(__builtin_fmaf(X[1].x, X[1].x, X[1].y * X[1].y)), ph2.y);
+}
+// bins I0 and I0 + 1 of a lane (k = lane + 64 i) from the last FFT pass's registers
+template <int L, int I0, typename Sink>
+__device__ __forceinline__ void polar_pair(const float2 (&v)[Geo<L>::E], const float2* twsl, int lane,
+                                           const Sink& sink) {
+    float2 X[2];
+    split_chunk_bp<L, 2, true, I0, false>(v, twsl, lane, X);
+    polar_of_pair(X, sink);
+}
+
+// Register overlap-add.  Slot s of a lane holds output positions 128 s + 2 lane + {0, 1} from
+// the current frame's start; the inverse FFT's last-pass register idx is slot last_slot(idx).
+// ola_add_by: acc[s] += z * gain(s), s rotated by ROT slots (REF_COMPAT's half swap: E / 2);
+// ola_add: the same with the lane's gains in registers gn, by slot; ola_shift: the D slots a
+// frame completes leave, the others move down and zeros come in.
+template <int L, int ROT = 0, typename G>
+__device__ __forceinline__ void ola_add_by(const float2 (&z)[Geo<L>::E], float2 (&acc)[Geo<L>::E], const G& gain) {
+    constexpr int E = Geo<L>::E;
+#pragma unroll
+    for (int idx = 0; idx < E; ++idx) {
+        const int cs = (last_slot<L>(idx) + ROT) & (E - 1);
+        const float2 g = gain(cs);
+        acc[cs].x = __builtin_fmaf(z[idx].x, g.x, acc[cs].x);
+        acc[cs].y = __builtin_fmaf(z[idx].y, g.y, acc[cs].y);
+    }
+}
+template <int L>
+__device__ __forceinline__ void ola_add(const float2 (&z)[Geo<L>::E], const float2 (&gn)[Geo<L>::E],
+                                        float2 (&acc)[Geo<L>::E]) {
+    ola_add_by<L>(z, acc, [&](int cs) { return gn[cs]; });
+}
+template <int D, int NS>
+__device__ __forceinline__ void ola_shift(float2 (&acc)[NS]) {
+#pragma unroll
+    for (int s = 0; s < NS; ++s) acc[s] = (s + D < NS) ? acc[(s + D < NS) ? s + D : 0] : make_float2(0.0f, 0.0f);
 }
 
 // bins of a lane: k = lane + 64 i (i < E), plus k = L on lane 0 (i == E)
@@ -515,11 +522,7 @@ __device__ __forceinline__ void synth_frame(const float2 (&sv)[Geo<L>::E + 1], b
                         constexpr int i0 = decltype(ig)::value * G;
                         i2v sc[G];
                         float2 f[G];
-            #ifdef PV_LANE0_PRESEL
-                if constexpr (true) {
-#else
-                if constexpr (L >= 1024) {
-#endif
+                        if constexpr (L >= 1024) {
 #pragma unroll
                             for (int j = 0; j < G; ++j) sc[j] = scn[j];
                         } else {

@@ -15,8 +15,9 @@
 // per CU (balanced runs, below), bound by the shared issue of the 3 waves per SIMD, not by
 // bytes (per-wave stamps).
 //
-// The per-frame arithmetic is k_std_analysis's (window, FFT, split, atan2, sqrt) and
-// k_synthesis's (synth_frame, register overlap-add, tails, seams) operation for operation,
+// The per-frame arithmetic calls the pieces k_std_analysis and k_synthesis are made of
+// (pv_frame.hpp: load_frame, win_mul, fft_run, bin_l_real, polar_pair; synth_frame, ola_add,
+// ola_shift; the tails and seams of pv_syn_run.hpp),
 // so the spectrum and the output are bit-identical to the split path (tests/test_gpu_fused.py)
 // — except MODE 4, whose output is the same sum rounded differently (within 1e-6).
 // MODE 4 (pitch exactly 2, L >= 256): output bin k' = 2 s takes source bin s and the odd
@@ -55,27 +56,13 @@ struct FuGeo {
     static_assert(O_SRC % 2 == 0 && O_TILE % 4 == 0, "alignment of the LDS carve-up");
 };
 
-template <int L, int MODE, int DT>
 // waves per SIMD k_fused is compiled for: 3 (<= 168 VGPRs; the balanced config-2 launch
 // holds exactly 3 workgroups per CU) — at 4 (<= 128) the L = 512 kernels spilled 6-12 VGPRs
 // to scratch; round 5 A/B: config 2 30.9 -> 30.1 us, and with the register split 29.6
-#ifndef PV_FUSED_WAVES
-#define PV_FUSED_WAVES 3
-#endif
-// 0: analyse every bin even without a spectrum output (A/B of the skip; same results)
-// 1: the real split straight from the FFT's last-pass registers (split_chunk_bp, as
-// k_std_analysis) instead of from a final image in LDS (0: the LDS-image split, A/B only)
-#ifndef PV_FUSED_BPSPLIT
-#define PV_FUSED_BPSPLIT 1
-#endif
-#ifndef PV_FUSED_SKIP_UNREAD
-#define PV_FUSED_SKIP_UNREAD 1
-#endif
-// 0: every frame's samples loaded whole (A/B of the shifted-register input; same results)
-#ifndef PV_FUSED_SHIFT
-#define PV_FUSED_SHIFT 1
-#endif
-__global__ __launch_bounds__(256, PV_FUSED_WAVES) void k_fused(FusedParams p) {
+constexpr int kFusedWaves = 3;
+
+template <int L, int MODE, int DT>
+__global__ __launch_bounds__(256, kFusedWaves) void k_fused(FusedParams p) {
     using G_ = Geo<L>;
     using FG = FuGeo<L>;
     constexpr int E = G_::E;
@@ -166,35 +153,9 @@ __global__ __launch_bounds__(256, PV_FUSED_WAVES) void k_fused(FusedParams p) {
     // inside [0, n) use vector loads, the last N/hop of a channel the bounds-checked path
     const long long lastfull = (p.aligned && p.n >= N) ? (p.n - N) / p.hop : -1;
     // registers E - DT .. E - 1 of frame t (its last 128 DT new sample pairs per lane)
-    auto load_tail = [&](int t, float2 (&xr)[E]) {
-        const long long base = (long long)t * p.hop;
-        if (t <= lastfull) {
-#pragma unroll
-            for (int q = E - DT; q < E; ++q) xr[q] = *reinterpret_cast<const float2*>(xc + base + 2 * (lane + 64 * q));
-        } else {
-#pragma unroll
-            for (int q = E - DT; q < E; ++q) {
-                const long long s = base + 2 * (lane + 64 * q);
-                xr[q].x = (s < p.n) ? xc[s] : 0.0f;
-                xr[q].y = (s + 1 < p.n) ? xc[s + 1] : 0.0f;
-            }
-        }
-    };
-    const bool shift_in = PV_FUSED_SHIFT && p.hop == 128 * DT;  // pitch: analysis hop = out hop
-    auto load = [&](int t, float2 (&xr)[E]) {
-        const long long base = (long long)t * p.hop;
-        if (t <= lastfull) {
-#pragma unroll
-            for (int q = 0; q < E; ++q) xr[q] = *reinterpret_cast<const float2*>(xc + base + 2 * (lane + 64 * q));
-        } else {
-#pragma unroll
-            for (int q = 0; q < E; ++q) {
-                const long long s = base + 2 * (lane + 64 * q);
-                xr[q].x = (s < p.n) ? xc[s] : 0.0f;
-                xr[q].y = (s + 1 < p.n) ? xc[s + 1] : 0.0f;
-            }
-        }
-    };
+    auto load_tail = [&](int t, float2 (&xr)[E]) { load_frame<E, E - DT>(xc, t, p.hop, p.n, lastfull, lane, xr); };
+    const bool shift_in = p.hop == 128 * DT;  // pitch: analysis hop = out hop
+    auto load = [&](int t, float2 (&xr)[E]) { load_frame<E>(xc, t, p.hop, p.n, lastfull, lane, xr); };
 
     // frame t0's samples are requested before the table set-up, whose latency hides theirs
     float2 xr[E];
@@ -273,11 +234,7 @@ __global__ __launch_bounds__(256, PV_FUSED_WAVES) void k_fused(FusedParams p) {
             {
                 const float2* wl = reinterpret_cast<const float2*>(winl) + lane;
 #pragma unroll
-                for (int q = 0; q < E; ++q) {
-                    const float2 wv = lds_ld(&wl[64 * q]);
-                    z[q].x = xr[q].x * wv.x;
-                    z[q].y = xr[q].y * wv.y;
-                }
+                for (int q = 0; q < E; ++q) win_mul(xr[q], lds_ld(&wl[64 * q]), z[q]);
             }
             if (u == 0) PV_STAMP(10);  // frame 0's samples have landed (F <= 7)
             // next frame's samples fly during this frame.  Pitch (analysis hop = out hop =
@@ -296,14 +253,9 @@ __global__ __launch_bounds__(256, PV_FUSED_WAVES) void k_fused(FusedParams p) {
                     load(t + 1, xr);
                 }
             }
-            // ---- analysis (k_std_analysis's operations): spectrum row out, kept in sv.  The
-            // split takes the partner bins from the last pass's registers by a lane reversal
-            // (split_chunk_bp; bit-identical to the LDS-image split)
-#if PV_FUSED_BPSPLIT
+            // ---- analysis (k_std_analysis's pieces): spectrum row out, kept in sv.  The split
+            // takes the partner bins from the last pass's registers by a lane reversal
             fft_run<L, false, false>(z, tile, twl, tw0, lane);
-#else
-            fft_run<L, false, true>(z, tile, twl, tw0, lane);
-#endif
             float2 sv[E + 1];
             // MODE 4: the half-size transform's input Y_s = |X_s| e^{2 i phi_s} = X_s^2 / |X_s|
             // (q = 1: the output phase is exactly 2 phi), bins s <= L/2 — no atan2, no sin/cos
@@ -312,16 +264,12 @@ __global__ __launch_bounds__(256, PV_FUSED_WAVES) void k_fused(FusedParams p) {
             // without a spectrum output only the bin pairs holding a bin some output bin reads
             // are analysed (pitch 2.0: bins 0 .. 256 of 512, so 3 of 4 pairs and no bin L): a
             // wave-uniform bound, the skipped bins' slots hold zeros that no gather reads
-            const int shi = (wspec || !PV_FUSED_SKIP_UNREAD) ? L : p.src_hi;
+            const int shi = wspec ? L : p.src_hi;
             // bin L (real: A = B = Z[0]) once, wave-uniformly, as k_std_analysis's bin_l_real:
             // its contract phase is +0 or pi, no atan2 (bit-identical to the generic bin)
             if (shi >= L) {
                 float magL, phL;
-#if PV_FUSED_BPSPLIT
                 bin_l_real<L, true>(z, twsl, magL, phL);
-#else
-                bin_l_real_tile<L, true>(tile, twsl, magL, phL);
-#endif
                 sv[E] = make_float2(magL, phL);
                 if (wspec && !p.packed) __builtin_nontemporal_store(f2v{magL, phL}, reinterpret_cast<f2v*>(&srow[L - lane]));
             } else {
@@ -336,13 +284,15 @@ __global__ __launch_bounds__(256, PV_FUSED_WAVES) void k_fused(FusedParams p) {
                     sv[i0] = sv[i0 + 1] = make_float2(0.0f, 0.0f);
                     return;
                 }
-                float2 X[CH];
-#if PV_FUSED_BPSPLIT
-                split_chunk_bp<L, CH, true, i0, false>(z, twsl, lane, X);
-#else
-                split_chunk<L, CH, true>(tile, twsl, lane, i0, X);
-#endif
+                auto put = [&](auto cc, float mag, float ph) {
+                    constexpr int i = i0 + decltype(cc)::value;
+                    sv[i] = make_float2(mag, ph);
+                    // bins 0..63 go out below (slot 0)
+                    if (wspec && i > 0) __builtin_nontemporal_store(f2v{mag, ph}, reinterpret_cast<f2v*>(&srow[64 * i]));
+                };
                 if constexpr (MODE == 4) {
+                    float2 X[CH];
+                    split_chunk_bp<L, CH, true, i0, false>(z, twsl, lane, X);
                     static_for<0, CH>([&](auto cc) {
                         constexpr int i = i0 + decltype(cc)::value;
                         if constexpr (i <= Geo<LH>::E) {
@@ -358,25 +308,10 @@ __global__ __launch_bounds__(256, PV_FUSED_WAVES) void k_fused(FusedParams p) {
                         }
                     });
                     if (!wspec) return;  // no row to write: no phase, no magnitude
+                    polar_of_pair(X, put);
+                } else {
+                    polar_pair<L, i0>(z, twsl, lane, put);
                 }
-                float phs[CH];
-                {
-                    const f2v ph2 = atan2_pv2(X[0].y, X[0].x, X[1].y, X[1].x);
-                    phs[0] = ph2.x;
-                    phs[1] = ph2.y;
-                }
-                static_for<0, CH>([&](auto cc) {
-                    constexpr int c2 = decltype(cc)::value;
-                    constexpr int i = i0 + c2;
-                    {
-                        const float ph = phs[c2];
-                        float mag = __builtin_amdgcn_sqrtf(__builtin_fmaf(X[c2].x, X[c2].x, X[c2].y * X[c2].y));
-                        mag *= 0.5f;  // X came out doubled (split_chunk TWICE)
-                        sv[i] = make_float2(mag, ph);
-                        // bins 0..63 go out below (slot 0)
-                        if (wspec && i > 0) __builtin_nontemporal_store(f2v{mag, ph}, reinterpret_cast<f2v*>(&srow[64 * i]));
-                    }
-                });
             });
             if (wspec) {
                 // slot 0: PV_SPEC_PACKED lane 0 carries bins 0 and L (both real)
@@ -412,13 +347,7 @@ __global__ __launch_bounds__(256, PV_FUSED_WAVES) void k_fused(FusedParams p) {
             } else {
             synth_frame<L, MODE, false, true, false, false, true>(sv, false, 0u, M, phprev, pmap, stb, tw0, tile,
                                                                   lane, z, ekr, jkr);
-            // ---- windowed overlap-add in registers
-#pragma unroll
-            for (int idx = 0; idx < E; ++idx) {
-                const int cs = last_slot<L>(idx);
-                acc[cs].x = __builtin_fmaf(z[idx].x, gn[cs].x, acc[cs].x);
-                acc[cs].y = __builtin_fmaf(z[idx].y, gn[cs].y, acc[cs].y);
-            }
+            ola_add<L>(z, gn, acc);  // windowed overlap-add in registers
             }
         }
         // positions [u*hs, (u+1)*hs) = slots 0..D-1 are final — except a workgroup's head
@@ -429,11 +358,7 @@ __global__ __launch_bounds__(256, PV_FUSED_WAVES) void k_fused(FusedParams p) {
         // the head positions of waves 1..3 are read back by close_seams_inline (intra-workgroup
         // seam): temporal stores keep them in L2 for that read (non-temporal ones stream past
         // it and the read-back waits for HBM)
-#ifdef PV_FUSED_NT_HEAD
-        const bool keep = false;
-#else
         const bool keep = (w > 0) && (u * hs < TL);
-#endif
 #pragma unroll
         for (int d = 0; d < D; ++d) {
             const long long gp = pb + 128 * d;
@@ -449,8 +374,7 @@ __global__ __launch_bounds__(256, PV_FUSED_WAVES) void k_fused(FusedParams p) {
                 if (gp + 1 < p.out_len) outc[gp + 1] = acc[d].y;
             }
         }
-#pragma unroll
-        for (int s = 0; s < NS; ++s) acc[s] = (s + D < NS) ? acc[(s + D < NS) ? s + D : 0] : make_float2(0.0f, 0.0f);
+        ola_shift<D>(acc);
         if (u < 6) PV_STAMP(3 + u);
     }
     PV_STAMP(11);  // frames end; slots 3..9 = frames 0..6

@@ -10,7 +10,7 @@
 // walks the channel in time,
 //   two analysis waves on alternate frames (window, FFT, split, atan2 -> a row in an LDS ring),
 //   one synthesis wave that reads the rows in order, makes the decisions inline (as k_rt does),
-//   keeps M in registers and runs k_synthesis's register overlap-add,
+//   keeps M in registers and runs the register overlap-add (ola_add, ola_shift),
 // and the path moves the samples alone: 4 hop + 4 out hop bytes per frame.
 //
 // Schedule: steps of two frames.  In step j analysis wave a transforms frame 2 j + a into ring
@@ -22,7 +22,8 @@
 // gives every SIMD one wave of each role.
 //
 // Results are the split path's bit for bit (tests/test_gpu_resident.py):
-//   rows      the operations of k_std_analysis (res_ana_frame, pv_resident.hpp);
+//   rows      the pieces k_std_analysis is made of (load_frame, win_mul; res_ana_frame:
+//             fft_run, bin_l_real, polar_pair — pv_frame.hpp, pv_resident.hpp);
 //   decisions the contract's one-rounding formula against the previous frame's phase for every
 //             frame, phi(-1) = 0 — what k_synthesis does inside a run and k_carry at a run's
 //             first frame; the revolution accumulator R = ((p M) mod q) / q is exact, so carrying
@@ -78,20 +79,7 @@ __global__ __launch_bounds__(64 * kResWaves, 3) void k_resident(ResidentParams p
         // frames whose N samples are all inside [0, n) take vector loads (x is aligned: the
         // host's predicate), the last N / hop of a channel the bounds-checked path
         const long long lastfull = (p.n >= N) ? (p.n - N) / p.hop : -1;
-        auto load = [&](int t, float2 (&xr)[E]) {
-            const long long base = (long long)t * p.hop;
-            if (t <= lastfull) {
-#pragma unroll
-                for (int q = 0; q < E; ++q) xr[q] = *reinterpret_cast<const float2*>(xc + base + 2 * (lane + 64 * q));
-            } else {
-#pragma unroll
-                for (int q = 0; q < E; ++q) {
-                    const long long s = base + 2 * (lane + 64 * q);
-                    xr[q].x = (s < p.n) ? xc[s] : 0.0f;
-                    xr[q].y = (s + 1 < p.n) ? xc[s + 1] : 0.0f;
-                }
-            }
-        };
+        auto load = [&](int t, float2 (&xr)[E]) { load_frame<E>(xc, t, p.hop, p.n, lastfull, lane, xr); };
         float2 wv[E];  // the window samples 2 (lane + 64 q) + {0, 1}, for the whole channel
         {
             const float2* w2 = reinterpret_cast<const float2*>(p.win) + lane;
@@ -105,10 +93,7 @@ __global__ __launch_bounds__(64 * kResWaves, 3) void k_resident(ResidentParams p
             if (t < frames) {
                 float2 z[E];
 #pragma unroll
-                for (int q = 0; q < E; ++q) {
-                    z[q].x = xr[q].x * wv[q].x;
-                    z[q].y = xr[q].y * wv[q].y;
-                }
+                for (int q = 0; q < E; ++q) win_mul(xr[q], wv[q], z[q]);
                 if (t + 2 < frames) load(t + 2, xr);  // in flight during this frame
                 res_ana_frame<L>(z, tile, twl, twsl, tw0, lane, ring + (t & (kResRing - 1)) * RG::ROW);
             }
@@ -171,8 +156,7 @@ __global__ __launch_bounds__(64 * kResWaves, 3) void k_resident(ResidentParams p
         if (tail_left > 0) {
 #pragma unroll
             for (int d = 0; d < D; ++d) v[d] = f2v{acc[d].x + tail[d].x, acc[d].y + tail[d].y};
-#pragma unroll
-            for (int s = 0; s < TM; ++s) tail[s] = (s + D < TM) ? tail[(s + D < TM) ? s + D : 0] : make_float2(0.0f, 0.0f);
+            ola_shift<D>(tail);
             tail_left -= D;
         }
 #pragma unroll
@@ -180,8 +164,7 @@ __global__ __launch_bounds__(64 * kResWaves, 3) void k_resident(ResidentParams p
             const long long gp = pos + 2 * lane + 128 * d;
             if (!CHECKED || gp + 1 < p.out_len) __builtin_nontemporal_store(v[d], reinterpret_cast<f2v*>(outc + gp));
         }
-#pragma unroll
-        for (int s = 0; s < NS; ++s) acc[s] = (s + D < NS) ? acc[(s + D < NS) ? s + D : 0] : make_float2(0.0f, 0.0f);
+        ola_shift<D>(acc);
     };
 
     for (int j = 0; j < nsteps; ++j) {
@@ -206,12 +189,7 @@ __global__ __launch_bounds__(64 * kResWaves, 3) void k_resident(ResidentParams p
             const unsigned tq = ((unsigned)t + 1u) & (p.q - 1u);
             synth_frame<L, 0, false, true, true, true, false, NoHook, TwReg<E>, false, NoEnv>(
                 sv, true, tq, M, phprev, pmap, stb, tw0, tile, lane, z, ekr, jkr, NoHook{}, twr, NoEnv{});
-#pragma unroll
-            for (int idx = 0; idx < E; ++idx) {
-                const int cs = last_slot<L>(idx);
-                acc[cs].x = __builtin_fmaf(z[idx].x, gn[cs].x, acc[cs].x);
-                acc[cs].y = __builtin_fmaf(z[idx].y, gn[cs].y, acc[cs].y);
-            }
+            ola_add<L>(z, gn, acc);
             flush((long long)t * hs, std::false_type{});
             ++u;
         }

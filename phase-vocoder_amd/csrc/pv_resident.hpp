@@ -1,9 +1,8 @@
 // pv_resident.hpp — the two frame bodies of the channel-resident STANDARD time stretch
 // (k_resident, pv_resident.hip): one analysis frame whose {mag, phase} row goes to LDS, and the
-// LDS carve-up the roles share.  Both are put together from the per-frame pieces the split
-// path's kernels are made of (pv_frame.hpp): fft_run, bin_l_real, split_chunk_bp, atan2_pv2 and
-// half_sqrt in k_std_analysis's order, so a row holds the bits that kernel writes to the
-// spectrum; the synthesis side calls synth_frame itself.
+// LDS carve-up the roles share.  The analysis frame calls the pieces k_std_analysis is made of
+// (pv_frame.hpp: fft_run, bin_l_real, polar_pair), so a row holds the bits that kernel writes to
+// the spectrum; the synthesis side calls synth_frame, ola_add and ola_shift itself.
 #pragma once
 #include "pv_frame.hpp"
 #include "pv_kernels.h"
@@ -44,11 +43,9 @@ __device__ __forceinline__ void res_ana_frame(float2 (&z)[Geo<L>::E], float2* ti
     bin_l_real<L, true>(z, twsl, magL, phL);
     static_for<0, E / 2>([&](auto ic) {
         constexpr int i0 = 2 * decltype(ic)::value;
-        float2 X[2];
-        split_chunk_bp<L, 2, true, i0, false>(z, twsl, lane, X);
-        const f2v ph2 = atan2_pv2(X[0].y, X[0].x, X[1].y, X[1].x);
-        row[lane + 64 * i0] = make_float2(half_sqrt(__builtin_fmaf(X[0].x, X[0].x, X[0].y * X[0].y)), ph2.x);
-        row[lane + 64 * (i0 + 1)] = make_float2(half_sqrt(__builtin_fmaf(X[1].x, X[1].x, X[1].y * X[1].y)), ph2.y);
+        polar_pair<L, i0>(z, twsl, lane, [&](auto cc, float mag, float ph) {
+            row[lane + 64 * (i0 + decltype(cc)::value)] = make_float2(mag, ph);
+        });
     });
     if (lane == 0) row[L] = make_float2(magL, phL);
     wave_lds_sync();

@@ -122,8 +122,7 @@ __global__ __launch_bounds__(256) void k_rt(RtParams p) {
             for (int q = 0; q < E; ++q) {
                 const float2 xv = lds_ld(&b2[64 * q]);
                 const float2 wv = lds_ld(&w2[64 * q]);
-                z[q].x = xv.x * wv.x;
-                z[q].y = xv.y * wv.y;
+                win_mul(xv, wv, z[q]);
             }
         }
         fft_run<L, false, false>(z, tile, twl, tw0, lane);  // the split reads the last pass's registers

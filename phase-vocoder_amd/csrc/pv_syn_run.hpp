@@ -350,15 +350,10 @@ __device__ __forceinline__ void syn_run(const SynParams& p, const SynCarve& sc, 
     // ROLA: register z[idx] = samples 2 (lane + 64 cr) + {0,1}; REF_COMPAT's half swap
     // moves raw slot cr to OLA slot cr + E/2 (mod E)
     auto ola_regs = [&](const float2 (&z)[E]) {
-#pragma unroll
-        for (int idx = 0; idx < E; ++idx) {
-            const int cr = last_slot<L>(idx);
-            const int cs = (MODE == 1) ? ((cr + E / 2) & (E - 1)) : cr;
-            const float2 g = GREG ? gn[GREG ? cs : 0]
-                                  : lds_ld(reinterpret_cast<const float2*>(gainl) + 64 * cs + lane);
-            acc[cs].x = __builtin_fmaf(z[idx].x, g.x, acc[cs].x);
-            acc[cs].y = __builtin_fmaf(z[idx].y, g.y, acc[cs].y);
-        }
+        if constexpr (ROLA)
+            ola_add_by<L, (MODE == 1) ? E / 2 : 0>(z, acc, [&](int cs) {
+                return GREG ? gn[GREG ? cs : 0] : lds_ld(reinterpret_cast<const float2*>(gainl) + 64 * cs + lane);
+            });
     };
     // ROLA flush of frame u: positions [u*hs, (u+1)*hs) = slots 0..D-1 are final
     auto flush_regs = [&](int u, auto fast_tag) {
@@ -375,8 +370,7 @@ __device__ __forceinline__ void syn_run(const SynParams& p, const SynCarve& sc, 
                 if (gp + 1 < p.out_len) outc[gp + 1] = acc[d].y;
             }
         }
-#pragma unroll
-        for (int s = 0; s < NS; ++s) acc[s] = (s + D < NS) ? acc[(s + D < NS) ? s + D : 0] : make_float2(0.0f, 0.0f);
+        ola_shift<D>(acc);
     };
 
     // formant and warp modes: the frame's log envelope row (k_envelope wrote it), loaded one

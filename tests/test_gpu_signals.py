@@ -124,7 +124,7 @@ def test_zoo_analysis_bit_exact(cuda, N, hop_div, effect, scale):
 
 
 @pytest.mark.xfail(strict=True, raises=AssertionError, reason="the analysis kernels compute the real split doubled (pv_frame.hpp "
-                   "split_chunk TWICE): where the contract's halved sums are fp32 denormals they round and the "
+                   "split_chunk_bp TWICE): where the contract's halved sums are fp32 denormals they round and the "
                    "doubled ones do not, and the hardware square root reads a denormal |2X|^2 as zero; bins of "
                    "|X| < 2^-62 only (DESIGN.md §3.2)")
 @pytest.mark.parametrize("N,hop_div,effect,scale", GEOMETRIES, ids=[_id((g, None)) for g in GEOMETRIES])
