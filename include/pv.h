@@ -87,7 +87,7 @@ extern "C" {
                                 pv_varresampler_* / pv_varresample / pv_varresample_steps /
                                 pv_varresample_length, pv_pitchmap_plan / pv_pitchmap_set /
                                 pv_pitchmap_output_length / pv_pitchmap_process,
-                                pv_resident_min_channels) */
+                                pv_resident_min_channels, pv_pitch_track / pv_pitch_correct_plan) */
 
 typedef struct pv_handle pv_handle;
 
@@ -603,6 +603,63 @@ long long pv_pitchmap_output_length(const pv_handle* h);
 pv_status pv_pitchmap_process(pv_handle* h, const float* x, long long ldx, long long n_samples, int channels,
                               int frames, pv_float2* spec, long long ld_spec, float* out, long long ldo,
                               void* stream);
+
+/* Pitch tracker and correction curve: the fundamental frequency of every
+ * analysed frame, and from it the pitch ratios that pv_pitchmap_set takes — analysis, track,
+ * correction curve, pv_pitchmap_process without the spectrum leaving the device.
+ * pv_pitch_track: dst[c*ld_dst + t] = {f0, strength}, c < channels, t < frames, from the rows'
+ *   magnitudes mag[k], k <= N/2; f0 in cycles per sample, {0, 0} for a frame without a pitch.
+ *   Any STANDARD handle (its window is the periodic Hann), natural or packed rows, n_samps in
+ *   [256, 2048]; spec, ld_spec as pv_onset_strength's.  Per frame, with integer lags
+ *   2 <= tau_min <= tau_max <= N/2 - 1 and kappa in (0, 1] (0: PV_PITCH_TRACK_DEFAULT_KAPPA):
+ *     mx = max mag[k] (a NaN magnitude counts as 0); mx 0 or not finite: {0, 0}.
+ *     s = 2^-e, e = mx's exponent taken from its bits (as at most 126);
+ *     P[k] = (mag[k] s)^2 (NaN: 0), evenly extended to N points; r = irfft(P, N), the circular
+ *     autocorrelation of the windowed frame; r[0] not above 0: {0, 0}.
+ *     rho[n] = r[n] / (r[0] g[n]), g[n] = 2/3 + cos(2 pi n / N) / 3: the window's own
+ *     autocorrelation divided out (Boersma's correction in its circular form).
+ *     A lag n in [tau_min, tau_max] is a candidate iff rho[n] > rho[n-1], rho[n] >= rho[n+1]
+ *     and rho[n] > 0; none: {0, 0}.  tau = the smallest candidate with rho >= kappa top, top the
+ *     largest candidate's rho (McLeod and Wyvill's key maximum).  With a, b, c = rho[tau-1],
+ *     rho[tau], rho[tau+1]: d = (a - c) / (2 (a - 2 b + c)), f0 = 1 / (tau + d),
+ *     strength = b - (a - c) d / 4.
+ *   fp32 in the kernel's order: tolerance bound (DESIGN.md §3.14 has the measured figures), no
+ *   bit-exact contract, except that scaling the input by a power of two changes no bit.  The
+ *   circular wrap grows with the lag: tau_max <= N/4 is the recommended range.  No voicing
+ *   decision is made: the strength is the caller's to threshold (white noise stays below 0.5).
+ *   No state between frames, nothing allocated; one launch (profile name: pitch), asynchronous
+ *   on `stream`, capturable from the first call.  Nothing beyond `frames` entries per row is
+ *   written.  channels = 0 or frames = 0 does nothing and returns PV_OK.
+ *   Refusals, each with a pv_last_error text: a NULL handle, spec or dst, lags outside the range
+ *   above, kappa outside [0, 1] or NaN, ld_spec < frames * spec_stride, ld_dst < frames with more
+ *   than one channel: PV_ERR_ARG; a REF_COMPAT handle: PV_ERR_UNSUPPORTED.
+ * pv_pitch_correct_plan: pure host, no handle, no GPU, fp64.  track: `frames` {f0, strength} of
+ *   one voice in host memory; ratio[u], u < n: the pitch ratio of output frame u, which sounds at
+ *   the analysis position pos[u] (NULL: pos[u] = u) — pv_pitchmap_set's two arrays.  cfg: a4,
+ *   the frequency of A4 in cycles per sample, > 0; scale_mask, bit i set = pitch class i is
+ *   allowed (0 = C), non-zero and below 2^12; strength_min, the voicing threshold; retune in
+ *   (0, 1], 1 snaps at once.  With t = clamp(floor(pos[u] + 0.5), 0, frames - 1), frame u is
+ *   voiced iff track[t].x is finite and > 0 and track[t].y >= strength_min (a NaN is unvoiced);
+ *   then note = 69 + 12 log2(f0 / a4), target = the nearest allowed semitone (the lower one on a
+ *   tie), c[u] = (target - note) / 12 octaves; unvoiced, c[u] = s[u-1]: the correction is held.
+ *   s[-1] = 0, s[u] = s[u-1] + retune (c[u] - s[u-1]), ratio[u] = 2^s[u] clamped to [1/4, 4].
+ *   PV_ERR_ARG with a pv_last_error text: a NULL track, cfg or ratio, frames or n < 1,
+ *   cfg->abi_version != PV_ABI_VERSION, a field of cfg outside its range, a position that is not
+ *   finite.
+ * One correction curve per call: one voice, or channels that share a voice, since pv_pitchmap_set
+ * is one map for all channels.  pv_rt and pv_main have no tracker. */
+#define PV_PITCH_TRACK_DEFAULT_KAPPA 0.9f
+typedef struct pv_pitch_correct {
+    int abi_version;      /* = PV_ABI_VERSION */
+    double a4;
+    unsigned scale_mask;
+    double strength_min;
+    double retune;
+} pv_pitch_correct;
+pv_status pv_pitch_track(pv_handle* h, const pv_float2* spec, long long ld_spec, int channels, int frames,
+                         int tau_min, int tau_max, float kappa, pv_float2* dst, long long ld_dst, void* stream);
+pv_status pv_pitch_correct_plan(const pv_float2* track, int frames, const double* pos, int n,
+                                const pv_pitch_correct* cfg, double* ratio);
 
 /* ---------------------------------------------------------------- real-time mode
  * A pv_rt streams `channels` mono channels through the STANDARD pipeline one callback at a

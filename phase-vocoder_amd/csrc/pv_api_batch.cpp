@@ -11,11 +11,6 @@ namespace pvhost {
 
 namespace {
 
-pv_status check_ld_spec(const pv_handle* h, int frames, long long ld_spec) {
-    if (ld_spec < (long long)frames * h->spec_stride) return fail(PV_ERR_ARG, "ld_spec < frames * spec_stride");
-    return PV_OK;
-}
-
 // the input rows can be read, and the output rows written, two samples at a time
 bool in_aligned(const pv_handle* h, const float* x, long long ldx) {
     return (((uintptr_t)x & 7) == 0) && (ldx % 2 == 0) && (h->hop % 2 == 0);
@@ -23,10 +18,6 @@ bool in_aligned(const pv_handle* h, const float* x, long long ldx) {
 bool out_aligned(const float* out, long long ldo) {
     return ((reinterpret_cast<uintptr_t>(out) & 7) == 0) && ((ldo & 1) == 0);
 }
-
-// the v3 pass table of the batched synthesis's inverse FFT (tw_syn_table: the second block at
-// L = 1024, the first otherwise)
-const float2* syn_v3_table(const pv_handle* h) { return h->d_tw_syn + (h->L_syn == 1024 ? h->L_syn : 0); }
 
 // what k_runsum and k_carry share; the carries and the segment state are the caller's
 pv::ScanParams scan_params(const pv_handle* h, const pv_float2* spec, long long ld_spec, int frames) {

@@ -10,6 +10,7 @@
 
 #include "../../include/pv.h"
 #include "pv_kernels.h"
+#include "pv_pitchtrack.hpp"
 #include "pv_resample.hpp"
 #include "pv_tables.hpp"
 #include "pv_varresample.hpp"
@@ -32,13 +33,13 @@ pv_status fail(pv_status s, const std::string& msg);
 
 // kernel ids of the per-launch profile and their names (pv_profile_read), index for index
 enum { KA, KRS, KC, KS, KSEAM, KCA, KRT, KF, KSL, KENV, KSF, KRES, KRTR, KSW, KON, KPK, KRST, KSR, KMS, KMC, KSM,
-       KVR, KRD, kNumKernels };
+       KVR, KRD, KPT, kNumKernels };
 inline constexpr const char* kKernelNames[] = {"analysis", "runsum", "carry", "synthesis", "seam",
                                                "compat_analysis", "rt", "fused", "synthesis_locked",
                                                "envelope", "synthesis_formant", "resample", "rt_resample",
                                                "synthesis_warp", "onset", "pick", "reset", "synthesis_reset",
                                                "map_sum", "map_carry", "synthesis_map", "var_resample",
-                                               "resident"};
+                                               "resident", "pitch"};
 static_assert(sizeof(kKernelNames) / sizeof(kKernelNames[0]) == kNumKernels, "one name per kernel id");
 
 // Move-only owner of one hipMalloc (Pinned: hipHostMalloc, device-mapped) allocation.  Converts
@@ -289,6 +290,14 @@ pv_status check_quality(const char* fn, int quality);
 pv_status check_std_stretch(const char* fn, const pv_handle* h);
 
 inline int nruns_of(const pv_handle* h, int frames) { return (frames + h->F - 1) / h->F; }
+// the caller's spectrum rows hold `frames` frames
+inline pv_status check_ld_spec(const pv_handle* h, int frames, long long ld_spec) {
+    if (ld_spec < (long long)frames * h->spec_stride) return fail(PV_ERR_ARG, "ld_spec < frames * spec_stride");
+    return PV_OK;
+}
+// the v3 pass table of the batched synthesis's inverse FFT (tw_syn_table: the second block at
+// L = 1024, the first otherwise)
+inline const float2* syn_v3_table(const pv_handle* h) { return h->d_tw_syn + (h->L_syn == 1024 ? h->L_syn : 0); }
 // the analysis keeps e_k in a register per lane (k_std_analysis EK_LANE)
 inline bool ek_lane_of(int hop_div, int bins) { return 64 % hop_div == 0 && bins >= 64; }
 // the single launch serves the handle's pv_process calls (phase locking, formant preservation,

@@ -469,4 +469,41 @@ bool pitchmap_plan(int N, int hop, const double* pos, const double* ratio, int n
     return true;
 }
 
+// The correction curve of a pitch track (pv_pitch_correct_plan): every voiced
+// frame's distance to the nearest allowed semitone (the lower one on a tie), held over the
+// unvoiced frames, through a one-pole smoother, as a pitch ratio per output frame.  fp64 only.
+bool pitch_correct_plan(const pv_float2* track, int frames, const double* pos, int n, const pv_pitch_correct& cfg,
+                        double* ratio) {
+    if (frames < 1 || n < 1) return false;
+    if (!(cfg.a4 > 0.0) || !std::isfinite(cfg.a4)) return false;
+    if (cfg.scale_mask == 0u || cfg.scale_mask >= 4096u) return false;
+    if (std::isnan(cfg.strength_min)) return false;
+    if (!(cfg.retune > 0.0 && cfg.retune <= 1.0)) return false;
+    if (pos)
+        for (int u = 0; u < n; ++u)
+            if (!std::isfinite(pos[u])) return false;
+    auto allowed = [&](long long m) { return (cfg.scale_mask >> (unsigned)(((m % 12) + 12) % 12)) & 1u; };
+    double s = 0.0;
+    for (int u = 0; u < n; ++u) {
+        const double x = std::floor((pos ? pos[u] : (double)u) + 0.5);
+        const int t = x <= 0.0 ? 0 : x >= (double)(frames - 1) ? frames - 1 : (int)x;
+        const double f0 = (double)track[t].x;
+        double c = s;
+        // (a NaN fails every comparison: unvoiced; so is a frame whose note is not finite, f0 / a4
+        // beyond the doubles)
+        const bool voiced = std::isfinite(f0) && f0 > 0.0 && (double)track[t].y >= cfg.strength_min;
+        const double note = voiced ? 69.0 + 12.0 * std::log2(f0 / cfg.a4) : 0.0;
+        if (voiced && std::isfinite(note)) {
+            long long lo = (long long)std::floor(note), hi = (long long)std::ceil(note);
+            while (!allowed(lo)) --lo;  // (at most 11 steps each: the mask is not empty)
+            while (!allowed(hi)) ++hi;
+            const double target = (note - (double)lo <= (double)hi - note) ? (double)lo : (double)hi;
+            c = (target - note) / 12.0;
+        }
+        s = s + cfg.retune * (c - s);
+        ratio[u] = std::min(4.0, std::max(0.25, std::exp2(s)));
+    }
+    return true;
+}
+
 }  // namespace pvtab

@@ -124,5 +124,11 @@ void var_window_table(int quality, int n, int len, std::vector<float>& tab);
 bool pitchmap_plan(int N, int hop, const double* pos, const double* ratio, int n, std::vector<double>& pos_s,
                    std::vector<long long>& step);
 
+// ---- pitch correction (pv_pitch_correct_plan): track [frames] {f0, strength}
+// -> ratio [n], one per output frame (pos: its analysis position, nullptr: u); false on a bad
+// argument (cfg's ranges, a position that is not finite, frames or n < 1)
+bool pitch_correct_plan(const pv_float2* track, int frames, const double* pos, int n, const pv_pitch_correct& cfg,
+                        double* ratio);
+
 }  // namespace pvtab
 #pragma GCC visibility pop

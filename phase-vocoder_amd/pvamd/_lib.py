@@ -18,6 +18,7 @@ PV_WINDOW_DEFAULT, PV_WINDOW_HAMMING_REF, PV_WINDOW_HANN_REF = 0, 1, 2
 PV_SPEC_NATURAL, PV_SPEC_PACKED = 0, 1
 PV_TRANSIENT_OFF, PV_TRANSIENT_FLAGS, PV_TRANSIENT_DETECT = 0, 1, 2
 PV_TRANSIENT_DEFAULT_THRESHOLD = 0.3  # include/pv.h
+PV_PITCH_TRACK_DEFAULT_KAPPA = 0.9  # include/pv.h
 ABI_VERSION = 5  # PV_ABI_VERSION of include/pv.h (pv_config / pv_info lead with it)
 
 
@@ -42,6 +43,11 @@ class pv_info(ctypes.Structure):
                 ("scale", ctypes.c_float), ("single_launch", ctypes.c_int),
                 ("single_launch_frames", ctypes.c_int),
                 ("lane_constants", ctypes.c_int), ("spec_layout", ctypes.c_int)]
+
+
+class pv_pitch_correct(ctypes.Structure):
+    _fields_ = [("abi_version", ctypes.c_int), ("a4", ctypes.c_double), ("scale_mask", ctypes.c_uint),
+                ("strength_min", ctypes.c_double), ("retune", ctypes.c_double)]
 
 
 def config(n_samps, hop_div, effect, scale, mode, max_channels, max_frames, device=0, window=PV_WINDOW_DEFAULT,
@@ -252,6 +258,10 @@ def lib():
     L.pv_pitchmap_output_length.restype = ll
     L.pv_pitchmap_process.argtypes = [vp, vp, ll, ll, i, i, vp, ll, vp, ll, vp]
     L.pv_pitchmap_process.restype = i
+    L.pv_pitch_track.argtypes = [vp, vp, ll, i, i, i, i, f, vp, ll, vp]
+    L.pv_pitch_track.restype = i
+    L.pv_pitch_correct_plan.argtypes = [vp, i, vp, i, ctypes.POINTER(pv_pitch_correct), vp]
+    L.pv_pitch_correct_plan.restype = i
     _lib = L
     return L
 

@@ -54,6 +54,48 @@ def timemap_split(pos):
     return idx, frac
 
 
+CHROMATIC = 0xFFF  # every pitch class (bit i: class i, 0 = C)
+MAJOR = 0xAB5      # C D E F G A B
+
+
+def pitch_correction(track, a4: float, scale=CHROMATIC, strength_min: float = 0.5, retune: float = 1.0,
+                     pos=None) -> np.ndarray:
+    """pv_pitch_correct_plan (pure host, no GPU): the {f0, strength} track of one voice
+    ([frames, 2], numpy or a tensor, `PhaseVocoder.pitch_track`'s row) -> the pitch ratios
+    (float64) that snap it to the scale, one per output frame, for `PhaseVocoder.set_pitch_map`.
+    a4: the frequency of A4 in cycles per sample (440 / sample rate); scale: a 12-bit mask (bit i
+    = pitch class i is allowed, 0 = C; `MAJOR`, `CHROMATIC`) or an iterable of pitch classes;
+    frames with a strength below strength_min hold the last correction; retune in (0, 1]: 1 snaps
+    at once, less glides there; pos: the analysis position of every output frame (None: frame u
+    for output u)."""
+    if hasattr(track, "detach"):
+        track = track.detach().cpu().numpy()
+    tr = np.ascontiguousarray(track, dtype=np.float32)
+    if tr.ndim != 2 or tr.shape[1] != 2:
+        raise ValueError("track must be [frames, 2]: one voice's {f0, strength}")
+    if isinstance(scale, (int, np.integer)):
+        mask = int(scale)
+    else:
+        mask = 0
+        for pc in scale:
+            if not 0 <= int(pc) < 12:
+                raise ValueError("a pitch class must be in 0 .. 11 (0 = C)")
+            mask |= 1 << int(pc)
+    if not 0 <= mask < 2 ** 32:
+        raise ValueError("scale mask out of range")
+    vp = ctypes.c_void_p
+    if pos is None:
+        n, pp = tr.shape[0], None
+    else:
+        pos = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1)
+        n, pp = int(pos.size), pos.ctypes.data_as(vp)
+    cfg = _lib.pv_pitch_correct(_lib.ABI_VERSION, float(a4), mask, float(strength_min), float(retune))
+    ratio = np.empty(max(n, 1), dtype=np.float64)
+    _lib.check(_lib.lib().pv_pitch_correct_plan(tr.ctypes.data_as(vp), int(tr.shape[0]), pp, n, ctypes.byref(cfg),
+                                                ratio.ctypes.data_as(vp)), "pv_pitch_correct_plan")
+    return ratio[:n]
+
+
 class PhaseVocoder:
     """`class PhaseVocoder` (src/phaseVocoder.h:9-139) on the MI355X HIP path."""
 
@@ -471,6 +513,35 @@ class PhaseVocoder:
                                                spec.stride(0) // 2 if spec is not None else 0, _ptr(out),
                                                out.stride(0), self._stream(stream)), "pv_pitchmap_process")
         return out, spec
+
+    # -------------------------------------------------------------- pitch tracker
+    def pitch_track(self, spec, fmin: float | None = None, fmax: float | None = None, kappa: float = 0.0,
+                    frames: int | None = None, stream=None, *, tau_min: int | None = None,
+                    tau_max: int | None = None):
+        """pv_pitch_track: spec [C, frames, spec_stride, 2] of a STANDARD handle -> [C, frames, 2]
+        float32 {f0, strength}: the fundamental frequency of every frame in cycles per sample
+        (0: none found) and the height of its autocorrelation peak (about 1 for a clean voice,
+        below 0.5 for noise: the caller's to threshold; see `pitch_correction`).  The search
+        range is fmin .. fmax in cycles per sample, as the lags ceil(1 / fmax) .. floor(1 / fmin),
+        or the lags themselves (tau_min=, tau_max=); they must lie in [2, N/2 - 1], and periods
+        up to N/4 are the recommended range.  kappa in (0, 1] (0: the default 0.9): how close to
+        the highest peak an earlier one must come to be taken for the period."""
+        torch = _torch()
+        if tau_min is None:
+            if fmax is None or not fmax > 0:
+                raise PVError(_lib.PV_ERR_ARG, "pitch_track: fmax (cycles per sample) must be > 0, or give tau_min")
+            tau_min = int(np.ceil(1.0 / fmax))
+        if tau_max is None:
+            if fmin is None or not fmin > 0:
+                raise PVError(_lib.PV_ERR_ARG, "pitch_track: fmin (cycles per sample) must be > 0, or give tau_max")
+            tau_max = int(min(np.floor(1.0 / fmin), 2 ** 30))
+        C = spec.shape[0]
+        frames = spec.shape[1] if frames is None else frames
+        dst = torch.zeros((C, frames, 2), dtype=torch.float32, device=spec.device)
+        self._call(self._L.pv_pitch_track(self._h, _ptr(spec), spec.stride(0) // 2, C, frames, int(tau_min),
+                                          int(tau_max), float(kappa), _ptr(dst), dst.stride(0) // 2,
+                                          self._stream(stream)), "pv_pitch_track")
+        return dst
 
     # -------------------------------------------------------------- pitch shift by resampling
     def reserve_pitch(self, quality: int = 0):
