@@ -16,9 +16,10 @@ def main():
     import torch.distributed as dist
 
     import pvref
+    from gpu_helpers import pv_frames
     from pvamd import STANDARD, TIME_SHIFT, PhaseVocoder
     from pvamd.dist import broadcast_tables, channel_shard
-    from test_gpu_parity import rms, synth
+    from signals import rms, synth
 
     total, n = int(sys.argv[1]), int(sys.argv[2])
     dist.init_process_group("gloo")
@@ -55,10 +56,6 @@ def main():
                           "finite": bool(np.isfinite(g).all())}), flush=True)
     finally:
         dist.destroy_process_group()
-
-
-def pv_frames(n, hop=256):
-    return max(1, -(-(n - hop) // hop))
 
 
 if __name__ == "__main__":

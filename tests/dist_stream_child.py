@@ -18,9 +18,10 @@ def main():
     import torch.distributed as dist
 
     import pvref
+    from gpu_helpers import pv_frames
     from pvamd import STANDARD, TIME_SHIFT, PhaseVocoder
     from pvamd.dist import assemble_segments, process_stream_segments
-    from test_gpu_parity import rms, synth
+    from signals import rms, synth
 
     n = int(sys.argv[1])
     dist.init_process_group("gloo")
@@ -49,10 +50,6 @@ def main():
                           "finite": bool(np.isfinite(got).all())}), flush=True)
     finally:
         dist.destroy_process_group()
-
-
-def pv_frames(n, hop=256):
-    return max(1, (n - hop + hop - 1) // hop)
 
 
 if __name__ == "__main__":

@@ -14,6 +14,7 @@ import functools
 import numpy as np
 
 import pvref
+from ref_cache import array, memo
 
 TWO_PI = 2.0 * np.pi
 FLOOR = 2.0 ** -30
@@ -87,22 +88,10 @@ def std_process_formant(x, N, hop_div, scale, order, frames=None):
     return out
 
 
-@functools.lru_cache(maxsize=None)
-def _cached(key, N, hop_div, scale, order, frames):
-    return std_process_formant(_inputs[key], N, hop_div, scale, order, frames)
-
-
-_inputs = {}
-
-
+@memo(x=array(np.float32), scale=float, order=int)
 def cached(x, N, hop_div, scale, order, frames=None):
     """std_process_formant, computed once per (input, configuration) and shared read-only."""
-    x = np.ascontiguousarray(x, np.float32)
-    key = hash(x.tobytes())
-    _inputs.setdefault(key, x)
-    out = _cached(key, N, hop_div, float(scale), int(order), frames)
-    out.setflags(write=False)
-    return out
+    return std_process_formant(x, N, hop_div, scale, order, frames)
 
 
 # ---------------------------------------------------------------- the formant property

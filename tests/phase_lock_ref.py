@@ -9,11 +9,10 @@ Locked frame: bin k is a peak iff mag[k] > mag[k'] (strict, on the fp32 magnitud
 k' in {k-2, k-1, k+1, k+2} inside [0, N/2]; own(k) is the nearest peak (the lower one on a
 tie; k itself if the frame has none); Y[k] = mag[k] exp(i (phi[k] + acc[own] - phi[own])).
 """
-import functools
-
 import numpy as np
 
 import pvref
+from ref_cache import array, memo
 
 TWO_PI = 2.0 * np.pi
 
@@ -88,22 +87,10 @@ def std_process_lock(x, N, hop_div, scale, lock, frames=None):
     return out
 
 
-@functools.lru_cache(maxsize=None)
-def _cached(key, N, hop_div, scale, lock, frames):
-    return std_process_lock(_inputs[key], N, hop_div, scale, lock, frames)
-
-
-_inputs = {}
-
-
+@memo(x=array(np.float32), scale=float, lock=bool)
 def cached(x, N, hop_div, scale, lock, frames=None):
     """std_process_lock, computed once per (input, configuration) and shared read-only."""
-    x = np.ascontiguousarray(x, np.float32)
-    key = hash(x.tobytes())
-    _inputs.setdefault(key, x)
-    out = _cached(key, N, hop_div, float(scale), bool(lock), frames)
-    out.setflags(write=False)
-    return out
+    return std_process_lock(x, N, hop_div, scale, lock, frames)
 
 
 def chirp(n=6144, f0=0.03, f1=0.11, amp=0.5):

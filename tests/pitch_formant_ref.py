@@ -12,13 +12,12 @@ i_k >= L on; lw[k] = le[i_k] + (r_k / hop) (le[min(i_k + 1, L)] - le[i_k]);
 |Y[k]| = mag[k] exp(lw[k] - le[k]); the phase is the stretch's, unlocked or locked, and the
 peaks and owners are those of the unscaled magnitudes.
 """
-import functools
-
 import numpy as np
 
 import pvref
 from formant_ref import log_envelope
 from phase_lock_ref import owners, peaks
+from ref_cache import array, memo
 
 TWO_PI = 2.0 * np.pi
 
@@ -85,19 +84,7 @@ def std_process_warp(x, N, hop_div, scale, lock, order, frames=None):
     return out
 
 
-@functools.lru_cache(maxsize=None)
-def _cached(key, N, hop_div, scale, lock, order, frames):
-    return std_process_warp(_inputs[key], N, hop_div, scale, lock, order, frames)
-
-
-_inputs = {}
-
-
+@memo(x=array(np.float32), scale=float, lock=bool, order=int)
 def cached(x, N, hop_div, scale, lock, order, frames=None):
     """std_process_warp, computed once per (input, configuration) and shared read-only."""
-    x = np.ascontiguousarray(x, np.float32)
-    key = hash(x.tobytes())
-    _inputs.setdefault(key, x)
-    out = _cached(key, N, hop_div, float(scale), bool(lock), int(order), frames)
-    out.setflags(write=False)
-    return out
+    return std_process_warp(x, N, hop_div, scale, lock, order, frames)

@@ -1,6 +1,6 @@
-"""Adversarial test signals and the per-hop parity check (a helper: no tests in here).
+"""The test signals, `rms` and the per-hop parity check (a helper: no tests in here).
 
-`zoo` is the set of inputs the synthesis and analysis parity tests run besides `synth`;
+`synth` is the three-tone generator of every parity test; `zoo` is the set of inputs the synthesis and analysis parity tests run besides `synth`;
 `assert_hop_parity` bounds every output hop of a result by the error the fp32 CPU port
 (oracle/pvport.c) has on the very same input, so that the bound follows the input's scale and
 conditioning instead of being one global RMS figure.
@@ -18,24 +18,36 @@ EPS32 = 2.0 ** -23  # one unit in the last place of an fp32 number in [1, 2)
 PORT_CAP = 2e-6
 
 
+def synth(n, seed, sr=44100, tones=3):
+    """configs 2-4 generator: 3 sines f~U[55,4000] Hz, a=0.1, + U(+-1e-3) noise."""
+    rng = np.random.default_rng(seed)
+    t = np.arange(n) / sr
+    x = np.zeros(n)
+    for _ in range(tones):
+        f = rng.uniform(55, 4000)
+        ph = rng.uniform(0, 2 * np.pi)
+        x += 0.1 * np.sin(2 * np.pi * f * t + ph)
+    x += rng.uniform(-1e-3, 1e-3, n)
+    return x.astype(np.float32)
+
+
 def zoo(n, N):
     """dict of float32 signals of length n (t = 0 .. n-1) for an analysis of N points, in the
     order of ZOO_NAMES:
 
-    synth     test_gpu_parity.synth(n, 31): three 0.1-amplitude sines + U(+-1e-3) noise
+    synth     synth(n, 31): three 0.1-amplitude sines + U(+-1e-3) noise
     noise_fs  default_rng(1).uniform(-0.99, 0.99, n): full-scale broadband
     impulses  0.9 where t % 397 == 5, else 0 (397 is prime: every hop phase is hit)
     dc        0.75
     nyquist   0.75 * (1 - 2 * (t & 1))
     bin_cos   0.5 * cos(2 pi (N/32) t / N): exactly centred on bin N/32
     square    +0.9 for (t // 50) even, -0.9 for odd (half-period 50 samples)
-    gaps      test_gpu_parity.synth(n, 5), zeroed where (t // 1500) is odd: digital silence
+    gaps      synth(n, 5), zeroed where (t // 1500) is odd: digital silence
               inside the stream, repeatedly
     step      0 for t < 5000, then 0.8
-    decay     test_gpu_parity.synth(n, 9) * 2^(-t/95), the product in fp64, then cast to
+    decay     synth(n, 9) * 2^(-t/95), the product in fp64, then cast to
               fp32: at n = 12000 the last ~400 samples are fp32 denormals, none is zero
     """
-    from test_gpu_parity import synth
     t = np.arange(n)
     z = {}
     z["synth"] = synth(n, 31)

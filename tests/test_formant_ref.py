@@ -11,24 +11,14 @@ import pytest
 import pvref
 from formant_ref import (FLOOR, INPUT_PEAK, formant_peak, log_envelope, pitch_map, std_process_formant, voice)
 from pvamd import _lib
+from signals import rms, synth
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 
 
-def rms(a, b):
-    return float(np.sqrt(np.mean((np.asarray(a, np.float64) - np.asarray(b, np.float64)) ** 2)))
-
-
-def tones(n, seed):
-    rng = np.random.default_rng(seed)
-    t = np.arange(n) / 44100.0
-    x = sum(0.1 * np.sin(2 * np.pi * rng.uniform(55, 4000) * t + rng.uniform(0, 2 * np.pi)) for _ in range(3))
-    return (x + rng.uniform(-1e-3, 1e-3, n)).astype(np.float32)
-
-
 @pytest.mark.parametrize("N,hop_div,scale", [(256, 4, 1.5), (512, 4, 0.75), (1024, 8, 1.37), (2048, 2, 2.0)])
 def test_reference_without_envelope_is_the_oracle(N, hop_div, scale):
-    x = tones(12 * N + 37, 21)
+    x = synth(12 * N + 37, 21)
     ref = pvref.std_process(x, N, hop_div, ord("p"), scale)
     got = std_process_formant(x, N, hop_div, scale, 0)
     assert got.shape == ref.shape
@@ -39,7 +29,7 @@ def test_reference_without_envelope_is_the_oracle(N, hop_div, scale):
 
 @pytest.mark.parametrize("N,hop_div,order", [(256, 4, 1), (512, 2, 32), (1024, 4, 256)])
 def test_ratio_one_is_the_plain_pitch_shift(N, hop_div, order):
-    x = tones(10 * N + 5, 22)
+    x = synth(10 * N + 5, 22)
     a = std_process_formant(x, N, hop_div, 1.0, order)
     b = std_process_formant(x, N, hop_div, 1.0, 0)
     assert np.max(np.abs(a - b)) <= 1e-9

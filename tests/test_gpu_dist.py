@@ -6,28 +6,21 @@ tables and refuses to compute until the broadcast delivers rank 0's, so the
 import must take effect), runs pv_process on its shard and checks it against the oracle."""
 import json
 import os
-import socket
 import subprocess
 import sys
 
 import pytest
+
+from gpu_helpers import free_port
 
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def test_two_rank_shards_with_table_broadcast(cuda):
     world, total, n = 2, 6, 60000
-    port = _free_port()
+    port = free_port()
     procs = []
     for r in range(world):
         env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK="0",

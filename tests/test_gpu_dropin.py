@@ -2,7 +2,6 @@
 the phaseVocoder.h drop-in), the Python mirror's per-frame reference methods, and the
 OVERLAPTEST identity path — each checked against the CPU oracle."""
 import os
-import struct
 import subprocess
 
 import numpy as np
@@ -10,25 +9,13 @@ import pytest
 
 import pvref
 from conftest import GOLDEN, ROOT
+from gpu_helpers import write_pcm16
 from pvamd import REF_COMPAT, STANDARD, TIME_SHIFT, PhaseVocoder, wav
+from signals import rms
 
 pytestmark = pytest.mark.gpu
 
 PV_MAIN = os.path.join(ROOT, "phase-vocoder_amd", "build", "pv_main")
-
-
-def write_pcm16(path, x):
-    """x = int16/32768 values (exact): write them back bit-exactly as mono 16-bit PCM."""
-    ints = np.round(np.asarray(x, np.float64) * 32768.0).astype("<i2")
-    body = ints.tobytes()
-    hdr = b"RIFF" + struct.pack("<i", 36 + len(body)) + b"WAVE"
-    hdr += b"fmt " + struct.pack("<ihhiihh", 16, 1, 1, 44100, 88200, 2, 16)
-    hdr += b"data" + struct.pack("<i", len(body))
-    open(path, "wb").write(hdr + body)
-
-
-def rms(a, b):
-    return float(np.sqrt(np.mean((np.asarray(a, np.float64) - np.asarray(b, np.float64)) ** 2)))
 
 
 @pytest.fixture(scope="module")

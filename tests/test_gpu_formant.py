@@ -10,10 +10,10 @@ import numpy as np
 import pytest
 
 from formant_ref import INPUT_PEAK, cached, formant_peak, log_envelope, voice
+from gpu_helpers import RMS_TOL, channel_errors, make_vocoder, run_segments, to_dev, wide
 from pvamd import PITCH_SHIFT, REF_COMPAT, STANDARD, TIME_SHIFT, Harmonizer, PhaseVocoder, _lib
 from pvamd._lib import PVError
-from test_gpu_parity import RMS_TOL, rms, synth, to_dev
-from test_gpu_segments import run_segments
+from signals import rms, synth
 
 pytestmark = pytest.mark.gpu
 
@@ -31,36 +31,19 @@ def inputs(n, seed=0):
     return np.stack([a, b, c])
 
 
-def wide(xs):
-    """device rows with a stride larger than the signals"""
-    import torch
-    buf = torch.full((xs.shape[0], xs.shape[1] + 40), 7.0, device="cuda")
-    buf[:, :xs.shape[1]] = to_dev(xs)
-    return buf[:, :xs.shape[1]]
-
-
 def length_for(N, hop_div, frames):
     return frames * (N // hop_div) + 13  # not a multiple of the hop
 
 
 def make(monkeypatch, N, hop_div, scale, F=8, frames=100, **kw):
-    monkeypatch.setenv("PV_RUN_FRAMES", str(F))
-    pv = PhaseVocoder(N, PITCH_SHIFT, scale, hop_div, mode=STANDARD, max_channels=C, max_frames=frames + 4, **kw)
-    assert pv.frames_per_run == F
-    return pv
+    return make_vocoder(monkeypatch, N, hop_div, PITCH_SHIFT, scale, F, max_frames=frames + 4, channels=C, **kw)
 
 
 def check_against_reference(out, xs, N, hop_div, scale, order, what=""):
-    g = out.cpu().numpy()
-    assert np.isfinite(g).all()
-    worst = 0.0
-    for c in range(xs.shape[0]):
-        ref = cached(xs[c], N, hop_div, scale, order)
-        assert g[c].shape == ref.shape
-        err = rms(g[c], ref)
-        worst = max(worst, err)
+    errs = channel_errors(out, lambda c: cached(xs[c], N, hop_div, scale, order), xs.shape[0])
+    for c, err in enumerate(errs):
         assert err <= RMS_TOL, f"channel {c}: rms {err}"
-    print(f"{what}N={N} hop_div={hop_div} scale={scale} order={order}: worst rms {worst:.3e}")
+    print(f"{what}N={N} hop_div={hop_div} scale={scale} order={order}: worst rms {max(errs):.3e}")
 
 
 # ---------------------------------------------------------------- the envelope kernel

@@ -20,9 +20,10 @@ import numpy as np
 import pytest
 
 import pvref
+from gpu_helpers import RMS_TOL
 from pvamd import PITCH_SHIFT, STANDARD, TIME_SHIFT, PhaseVocoder
 from pvamd import _lib
-from test_gpu_parity import RMS_TOL, rms
+from signals import rms
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bench import check_channels, cpu_share, synth_channels_np  # noqa: E402

@@ -6,9 +6,9 @@ import numpy as np
 import pytest
 
 import pvref
+from gpu_helpers import RMS_TOL, pv_frames, to_dev
 from pvamd import PITCH_SHIFT, STANDARD, TIME_SHIFT, PhaseVocoder
-from signals import assert_hop_parity
-from test_gpu_parity import RMS_TOL, rms, synth, to_dev
+from signals import assert_hop_parity, rms, synth
 
 pytestmark = pytest.mark.gpu
 
@@ -40,10 +40,6 @@ def test_config2_full_stream(cuda):
     _, ph = pvref.std_analysis(x, 1024, 256, frames)
     s = spec.cpu().numpy()[0, :frames, :513]
     assert np.array_equal(s[..., 1].view(np.uint32), ph.view(np.uint32))
-
-
-def pv_frames(n, hop=256):
-    return max(1, -(-(n - hop) // hop))
 
 
 @pytest.mark.parametrize("N,hop_div,effect,scale", [

@@ -5,25 +5,11 @@ import numpy as np
 import pytest
 
 import pvref
+from gpu_helpers import RMS_TOL
 from pvamd import PITCH_SHIFT, STANDARD, Harmonizer, PhaseVocoder
+from signals import rms, synth
 
 pytestmark = pytest.mark.gpu
-
-RMS_TOL = 1e-5
-
-
-def synth(n, seed, sr=44100):
-    rng = np.random.default_rng(seed)
-    t = np.arange(n) / sr
-    x = np.zeros(n)
-    for _ in range(3):
-        x += 0.1 * np.sin(2 * np.pi * rng.uniform(55, 4000) * t + rng.uniform(0, 2 * np.pi))
-    x += rng.uniform(-1e-3, 1e-3, n)
-    return x.astype(np.float32)
-
-
-def rms(a, b):
-    return float(np.sqrt(np.mean((np.asarray(a, np.float64) - np.asarray(b, np.float64)) ** 2)))
 
 
 @pytest.mark.parametrize("N,ratios", [(1024, [1.25, 1.5, 0.75]), (512, [2.0, 1.0]),

@@ -7,15 +7,11 @@ import numpy as np
 import pytest
 
 import pvref
+from gpu_helpers import RMS_TOL, pv_frames, to_dev
 from pvamd import PITCH_SHIFT, STANDARD, TIME_SHIFT, PhaseVocoder
-from test_gpu_parity import RMS_TOL, rms, synth, to_dev
+from signals import rms, synth
 
 pytestmark = pytest.mark.gpu
-
-
-def pv_frames(n, hop):
-    return max(1, -(-(n - hop) // hop))
-
 
 CASES = [  # (N, hop_div, effect, scale, lane constants expected)
     (1024, 4, TIME_SHIFT, 0.5, 1),     # config 3: q = 2

@@ -9,9 +9,10 @@ import numpy as np
 import pytest
 
 import pvref
+from gpu_helpers import RMS_TOL, to_dev
 from pvamd import PITCH_SHIFT, STANDARD, TIME_SHIFT, PhaseVocoder
 from pvamd import _lib
-from test_gpu_parity import RMS_TOL, rms, synth, to_dev
+from signals import rms, synth
 
 pytestmark = pytest.mark.gpu
 

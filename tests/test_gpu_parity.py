@@ -3,34 +3,11 @@ import numpy as np
 import pytest
 
 import pvref
+from gpu_helpers import RMS_TOL, pv_frames, to_dev
 from pvamd import PhaseVocoder, REF_COMPAT, STANDARD, TIME_SHIFT, PITCH_SHIFT
-from signals import assert_hop_parity
+from signals import assert_hop_parity, rms, synth
 
 pytestmark = pytest.mark.gpu
-
-RMS_TOL = 1e-5  # BASELINE.json north_star: <= 1e-5 RMS per sample vs the CPU reference
-
-
-def synth(n, seed, sr=44100, tones=3):
-    """configs 2-4 generator: 3 sines f~U[55,4000] Hz, a=0.1, + U(+-1e-3) noise."""
-    rng = np.random.default_rng(seed)
-    t = np.arange(n) / sr
-    x = np.zeros(n)
-    for _ in range(tones):
-        f = rng.uniform(55, 4000)
-        ph = rng.uniform(0, 2 * np.pi)
-        x += 0.1 * np.sin(2 * np.pi * f * t + ph)
-    x += rng.uniform(-1e-3, 1e-3, n)
-    return x.astype(np.float32)
-
-
-def to_dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def rms(a, b):
-    return float(np.sqrt(np.mean((np.asarray(a, np.float64) - np.asarray(b, np.float64)) ** 2)))
 
 
 # (the analysis's frame-loop forms: 1024/4, 512/4, 1024/2, 512/2 the register rotation in
@@ -121,10 +98,6 @@ def test_split_path_without_spectrum_output(cuda, N, hop_div, effect, scale, pac
     for c in range(C):
         assert g2[c].shape == ref[c].shape and rms(g2[c], ref[c]) <= RMS_TOL, f"ch{c}"
         assert_hop_parity(g2[c], ref64[c], port[c], pv.outHopSize, what=f"ch{c}")
-
-
-def pv_frames(n, hop):
-    return max(1, -(-(n - hop) // hop))
 
 
 def test_split_equals_fused(cuda):

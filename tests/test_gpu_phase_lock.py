@@ -4,21 +4,22 @@ synthesis, spectrum / no spectrum / packed rows / analysis + resynthesis, stream
 the toggle and the refusals.  Runs of 8 frames (PV_RUN_FRAMES) and 76 frames per channel: 10
 runs, 3 workgroups (two workgroup seams), the last run partial."""
 import ctypes
+import functools
 
 import numpy as np
 import pytest
 
 import pvref
+from gpu_helpers import LOCK_INPUTS, RMS_TOL, channel_errors, make_vocoder, run_segments, stretch_inputs, to_dev
 from phase_lock_ref import cached, chirp, mean_envelope
 from pvamd import PITCH_SHIFT, REF_COMPAT, STANDARD, TIME_SHIFT, PhaseVocoder, _lib
 from pvamd._lib import PVError
-from test_gpu_parity import RMS_TOL, rms, synth, to_dev
-from test_gpu_segments import run_segments
+from signals import rms, synth
 
 pytestmark = pytest.mark.gpu
 
 C = 3
-FRAMES = 76
+FRAMES = LOCK_INPUTS["frames"]
 
 CASES = [
     (256, 4, 1.5),    # small N, LDS-ring overlap-add
@@ -33,27 +34,16 @@ CASES = [
 ]
 
 
-def inputs(N, hop_div):
-    hop = N // hop_div
-    n = FRAMES * hop + 13  # not a multiple of the hop
-    assert pvref.num_frames(n, hop) == FRAMES
-    return np.stack([synth(n, 9100 + 7 * c + N) for c in range(C)])
+inputs = functools.partial(stretch_inputs, **LOCK_INPUTS, channels=C)
 
 
 def make(monkeypatch, N, hop_div, scale, **kw):
-    monkeypatch.setenv("PV_RUN_FRAMES", "8")
-    pv = PhaseVocoder(N, TIME_SHIFT, scale, hop_div, mode=STANDARD, max_channels=C, max_frames=FRAMES + 4, **kw)
-    assert pv.frames_per_run == 8
-    return pv
+    return make_vocoder(monkeypatch, N, hop_div, TIME_SHIFT, scale, max_frames=FRAMES + 4, channels=C, **kw)
 
 
 def check_against_reference(out, xs, N, hop_div, scale):
-    g = out.cpu().numpy()
-    assert np.isfinite(g).all()
-    for c in range(xs.shape[0]):
-        ref = cached(xs[c], N, hop_div, scale, True)
-        assert g[c].shape == ref.shape
-        err = rms(g[c], ref)
+    errs = channel_errors(out, lambda c: cached(xs[c], N, hop_div, scale, True), xs.shape[0])
+    for c, err in enumerate(errs):
         print(f"N={N} hop_div={hop_div} scale={scale} channel {c}: rms {err:.3e}")
         assert err <= RMS_TOL, f"channel {c}: rms {err}"
 

@@ -16,11 +16,11 @@ import pytest
 
 import resample_ref as rr
 from formant_ref import INPUT_PEAK, formant_peak, voice
+from gpu_helpers import RMS_TOL, channel_errors, make_vocoder, run_segments, to_dev
 from pitch_formant_ref import cached
 from pvamd import PITCH_SHIFT, REF_COMPAT, STANDARD, TIME_SHIFT, PhaseVocoder, _lib
 from pvamd._lib import PVError
-from test_gpu_parity import RMS_TOL, rms, to_dev
-from test_gpu_segments import run_segments
+from signals import rms
 
 pytestmark = pytest.mark.gpu
 
@@ -43,21 +43,11 @@ def inputs(N, hop_div):
 
 
 def make(monkeypatch, N, hop_div, scale, frames, **kw):
-    monkeypatch.setenv("PV_RUN_FRAMES", str(F))
-    pv = PhaseVocoder(N, TIME_SHIFT, scale, hop_div, mode=STANDARD, max_channels=C, max_frames=frames + 4, **kw)
-    assert pv.frames_per_run == F
-    return pv
+    return make_vocoder(monkeypatch, N, hop_div, TIME_SHIFT, scale, F, max_frames=frames + 4, channels=C, **kw)
 
 
 def check_against_reference(out, xs, N, hop_div, scale, lock, order, what=""):
-    g = out.cpu().numpy()
-    assert np.isfinite(g).all()
-    worst = 0.0
-    for c in range(xs.shape[0]):
-        ref = cached(xs[c], N, hop_div, scale, lock, order)
-        assert g[c].shape == ref.shape
-        err = rms(g[c], ref)
-        worst = max(worst, err)
+    worst = max(channel_errors(out, lambda c: cached(xs[c], N, hop_div, scale, lock, order), xs.shape[0]))
     print(f"{what}N={N} hop_div={hop_div} scale={scale} order={order} lock={lock}: worst channel rms {worst:.3e}")
     assert worst <= RMS_TOL
     return worst

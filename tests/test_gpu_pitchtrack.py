@@ -14,8 +14,8 @@ import numpy as np
 import pytest
 
 import pitchtrack_ref as pr
+from gpu_helpers import make_vocoder, status_of, wide
 from pvamd import MAJOR, REF_COMPAT, STANDARD, TIME_SHIFT, PhaseVocoder, _lib, pitch_correction
-from pvamd._lib import PVError
 
 pytestmark = pytest.mark.gpu
 
@@ -24,20 +24,9 @@ FRAMES = pr.PARITY_FRAMES
 LAYOUTS = [_lib.PV_SPEC_NATURAL, _lib.PV_SPEC_PACKED]
 
 
-def wide(xs):
-    """device rows with a stride larger than the signals"""
-    import torch
-    buf = torch.full((xs.shape[0], xs.shape[1] + 40), 7.0, device="cuda")
-    buf[:, :xs.shape[1]] = torch.from_numpy(np.array(xs, np.float32)).cuda()
-    return buf[:, :xs.shape[1]]
-
-
 def make(monkeypatch, N, F=8, frames=FRAMES, layout=_lib.PV_SPEC_NATURAL, channels=C, **kw):
-    monkeypatch.setenv("PV_RUN_FRAMES", str(F))
-    pv = PhaseVocoder(N, TIME_SHIFT, 1.0, 4, mode=STANDARD, max_channels=channels, max_frames=frames + 4,
-                      spec_layout=layout, **kw)
-    assert pv.frames_per_run == F
-    return pv
+    return make_vocoder(monkeypatch, N, 4, TIME_SHIFT, 1.0, F, max_frames=frames + 4, channels=channels,
+                        spec_layout=layout, **kw)
 
 
 def magnitudes(pv, spec):
@@ -179,15 +168,6 @@ def test_pitch_track_captures_into_a_graph(cuda, monkeypatch):
         g.replay()
         torch.cuda.synchronize()
         assert torch.equal(dst, ref)
-
-
-def status_of(fn):
-    try:
-        fn()
-    except PVError as e:
-        assert len(str(e)) > 0
-        return e.status
-    return _lib.PV_OK
 
 
 def test_pitch_track_refusals(cuda):

@@ -3,8 +3,9 @@ pv_process call's launches carry hipEvents, and the outputs do not depend on it.
 import numpy as np
 import pytest
 
+from gpu_helpers import to_dev
 from pvamd import PITCH_SHIFT, STANDARD, TIME_SHIFT, PhaseVocoder
-from test_gpu_parity import synth, to_dev
+from signals import synth
 
 pytestmark = pytest.mark.gpu
 

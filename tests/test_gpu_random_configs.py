@@ -7,9 +7,9 @@ import numpy as np
 import pytest
 
 import pvref
+from gpu_helpers import RMS_TOL, oracle_stream, run_segments, to_dev
 from pvamd import PITCH_SHIFT, REF_COMPAT, STANDARD, TIME_SHIFT, PhaseVocoder
-from signals import assert_hop_parity
-from test_gpu_parity import RMS_TOL, rms, synth
+from signals import assert_hop_parity, rms, synth
 
 pytestmark = pytest.mark.gpu
 
@@ -69,7 +69,6 @@ def test_random_configuration_in_segments(cuda, seed):
     """The same draws (STANDARD) as 2-5 consecutive frame segments (pv_segment_*): the
     assembled output equals the whole stream's up to the seams' summation order."""
     import torch
-    from test_gpu_segments import run_segments
     N, hop_div, compat, effect, scale, C, n = draw(3000 + seed)
     hop = N // hop_div
     if compat or (effect == TIME_SHIFT and int(np.float32(scale) * np.float32(hop)) > N):
@@ -89,7 +88,6 @@ def test_random_real_time_configuration(cuda, seed):
     """Real-time mode (pv_rt_*) on random draws: the stream pushed in random-size blocks of
     whole hops equals the oracle's offline pipeline over the zero-prefixed stream."""
     from pvamd import RealTimeVocoder
-    from test_gpu_rt import dev, oracle_stream
     rng = np.random.default_rng(9000 + seed)
     N = int(rng.choice([256, 512, 1024, 2048]))
     hop_div = int(rng.choice([2, 4, 4, 8]))
@@ -102,7 +100,7 @@ def test_random_real_time_configuration(cuda, seed):
     x = synth(K * hop, 9500 + seed)
     rt = RealTimeVocoder(N, effect, scale, hop_div, channels=1)
     hs = rt.outHopSize
-    xd = dev(x)
+    xd = to_dev(x)
     outs, j = [], 0
     while j < K:
         m = int(min(K - j, rng.integers(1, 5)))

@@ -4,23 +4,26 @@ stretch, locked or not, then the resampling by out_hop / hop) against the refere
 of tests/phase_lock_ref.py's stretch.  n_in = 20011 is several workgroup tiles and a partial one
 at every ratio; the pitch cases run 76 frames in runs of 8 (PV_RUN_FRAMES), as
 test_gpu_phase_lock does, and share its cached references."""
+import functools
+
 import numpy as np
 import pytest
 
 import pvref
 import resample_ref as rr
+from gpu_helpers import (LOCK_INPUTS, RMS_TOL, make_vocoder, run_padded, stretch_inputs, to_dev, to_dev_copy,
+                         write_pcm16)
 from phase_lock_ref import cached, chirp, mean_envelope
 from pvamd import PITCH_SHIFT, REF_COMPAT, STANDARD, TIME_SHIFT, PhaseVocoder, Resampler, _lib
 from pvamd._lib import PVError
-from test_gpu_parity import RMS_TOL, rms, synth, to_dev
+from signals import rms, synth
 
 pytestmark = pytest.mark.gpu
 
 C = 3
 N_IN = 20011
 PAD = 37
-SENTINEL = -77.25
-FRAMES = 76
+FRAMES = LOCK_INPUTS["frames"]
 
 RESAMPLE_CASES = [(3, 2, 0), (3, 4, 0), (2, 1, 0), (1, 4, 0), (4, 1, 0), (701, 512, 0), (127, 170, 0), (3, 2, 1),
                   (127, 170, 1)]
@@ -33,32 +36,6 @@ def signal(n=N_IN):
         _xs[n] = np.stack([synth(n, 3300 + 11 * c) for c in range(C)])
         _xs[n].setflags(write=False)
     return _xs[n]
-
-
-def dev(a):
-    """a device copy (the shared host arrays are read-only)"""
-    return to_dev(np.array(a))
-
-
-def padded_input(xs, pad):
-    """rows of xs in a [C, n + pad] tensor whose padding is NaN"""
-    import torch
-    buf = torch.full((xs.shape[0], xs.shape[1] + pad), float("nan"), dtype=torch.float32, device="cuda")
-    buf[:, :xs.shape[1]] = dev(xs)
-    return buf
-
-
-def run_padded(rs, xs, pad=PAD):
-    """resample the rows of xs from NaN-padded rows into sentinel-padded rows; returns the
-    output rows after checking that the sentinel survived"""
-    import torch
-    n = xs.shape[1]
-    buf = padded_input(xs, pad)
-    n_out = rs.length(n)
-    ybuf = torch.full((xs.shape[0], n_out + 5), SENTINEL, dtype=torch.float32, device="cuda")
-    rs(buf[:, :n], out=ybuf[:, :n_out])
-    assert (ybuf[:, n_out:] == SENTINEL).all()
-    return ybuf[:, :n_out].cpu().numpy()
 
 
 def check_parity(p, q, quality, pad):
@@ -95,7 +72,7 @@ def test_resample_short_inputs(cuda, p, q, quality):
     W = rr.half_width(p, q, quality)
     for n in (1, W - 1):
         xs = signal()[:, 100:100 + n]
-        g = run_padded(rs, xs)
+        g = run_padded(rs, xs, PAD)
         ref = rr.resample(xs, p, q, quality)
         assert g.shape == ref.shape == (C, rr.out_length(p, q, n))
         assert np.max(np.abs(g - ref)) <= 1e-6
@@ -108,7 +85,7 @@ def test_resample_short_inputs(cuda, p, q, quality):
 
 def test_resample_twice_is_the_same_bits(cuda):
     import torch
-    xd = dev(signal())
+    xd = to_dev_copy(signal())
     rs = Resampler(701, 512, 0)
     assert torch.equal(rs(xd), rs(xd))
 
@@ -117,9 +94,9 @@ def test_resample_ratio_one_is_a_copy(cuda):
     import torch
     xs = signal()
     for p, q in ((1, 1), (512, 512)):
-        g = run_padded(Resampler(p, q, 1), xs)
+        g = run_padded(Resampler(p, q, 1), xs, PAD)
         assert np.array_equal(g, xs)
-    x1 = dev(xs[0])
+    x1 = to_dev_copy(xs[0])
     assert torch.equal(Resampler(5, 5)(x1), x1)
 
 
@@ -146,7 +123,7 @@ def test_resampler_refusals(cuda):
 def test_resample_in_a_graph(cuda):
     """one pv_resample call captured on a side stream and replayed"""
     import torch
-    xd = dev(signal())
+    xd = to_dev_copy(signal())
     rs = Resampler(3, 2, 0)
     eager = rs(xd)
     out = torch.empty_like(eager)
@@ -165,19 +142,11 @@ def test_resample_in_a_graph(cuda):
 
 
 # ------------------------------------------------------------------ pv_pitch_process
-def inputs(N, hop_div):
-    """test_gpu_phase_lock's inputs (its locked references are cached under the same key)"""
-    hop = N // hop_div
-    n = FRAMES * hop + 13
-    assert pvref.num_frames(n, hop) == FRAMES
-    return np.stack([synth(n, 9100 + 7 * c + N) for c in range(C)])
+inputs = functools.partial(stretch_inputs, **LOCK_INPUTS, channels=C)  # (the locked references are shared)
 
 
 def make(monkeypatch, N, hop_div, scale, **kw):
-    monkeypatch.setenv("PV_RUN_FRAMES", "8")
-    pv = PhaseVocoder(N, TIME_SHIFT, scale, hop_div, mode=STANDARD, max_channels=C, max_frames=FRAMES + 4, **kw)
-    assert pv.frames_per_run == 8
-    return pv
+    return make_vocoder(monkeypatch, N, hop_div, TIME_SHIFT, scale, max_frames=FRAMES + 4, channels=C, **kw)
 
 
 PITCH_CASES = [
@@ -301,7 +270,6 @@ def test_pv_main_pitch_resample(cuda, tmp_path):
 
     from conftest import GOLDEN, ROOT
     from phase_lock_ref import std_process_lock
-    from test_gpu_dropin import write_pcm16
     pv_main = os.path.join(ROOT, "phase-vocoder_amd", "build", "pv_main")
     x = np.load(os.path.join(GOLDEN, "sine440_ch0_32768.npy"))
     wav_in, dump = str(tmp_path / "in.wav"), str(tmp_path / "o.f32")

@@ -8,10 +8,9 @@ import ctypes
 import numpy as np
 import pytest
 
+from gpu_helpers import ZOO_SAMPLES, to_dev, zoo_input, zoo_reference
 from pvamd import STANDARD, TIME_SHIFT, PhaseVocoder, _lib
-from signals import ZOO_NAMES, assert_hop_parity
-from test_gpu_parity import synth, to_dev
-from test_gpu_signals import N_SAMPLES, _reference, _rows
+from signals import ZOO_NAMES, assert_hop_parity, synth
 
 pytestmark = pytest.mark.gpu
 
@@ -119,18 +118,18 @@ def test_longer_runs(cuda, monkeypatch):
 def test_signal_zoo(cuda, monkeypatch):
     """the ten adversarial signals as channels: the split path's bits, and on the same run the
     oracle's per-hop bound (as tests/test_gpu_signals.py)"""
-    xs = _rows(N_SAMPLES, N)
-    frames = -(-(N_SAMPLES - HOP) // HOP)
+    xs = zoo_input(ZOO_SAMPLES, N)
+    frames = -(-(ZOO_SAMPLES - HOP) // HOP)
     # (12001 samples in rows of an even stride)
     xd = to_dev(np.concatenate([xs, np.zeros((len(xs), 1), np.float32)], axis=1))
-    want, _, ks = _run(_vocoder(monkeypatch, "0", len(xs), frames), xd, n_samples=N_SAMPLES, spectrum=False)
+    want, _, ks = _run(_vocoder(monkeypatch, "0", len(xs), frames), xd, n_samples=ZOO_SAMPLES, spectrum=False)
     pr = _vocoder(monkeypatch, "1", len(xs), frames)
-    got, _, kr = _run(pr, xd, n_samples=N_SAMPLES, spectrum=False)
+    got, _, kr = _run(pr, xd, n_samples=ZOO_SAMPLES, spectrum=False)
     _assert_split(ks)
     _assert_resident(kr)
     _same(got, want, "zoo")
     g = got.cpu().numpy()
-    refs, port, hs = _reference(N, HOP_DIV, TIME_SHIFT, SCALE)
+    refs, port, hs = zoo_reference(N, HOP_DIV, TIME_SHIFT, SCALE)
     assert hs == pr.outHopSize and np.isfinite(g).all()
     for c, name in enumerate(ZOO_NAMES):
         assert g[c].shape == refs[c].shape

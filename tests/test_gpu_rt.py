@@ -6,37 +6,11 @@ import numpy as np
 import pytest
 
 import pvref
+from gpu_helpers import RMS_TOL, oracle_stream, to_dev
 from pvamd import PITCH_SHIFT, STANDARD, TIME_SHIFT, PhaseVocoder, RealTimeVocoder
-from signals import assert_hop_parity
+from signals import assert_hop_parity, rms, synth
 
 pytestmark = pytest.mark.gpu
-
-RMS_TOL = 1e-5  # BASELINE.json north_star: <= 1e-5 RMS per sample vs the CPU reference
-
-
-def synth(n, seed, sr=44100):
-    rng = np.random.default_rng(seed)
-    t = np.arange(n) / sr
-    x = np.zeros(n)
-    for _ in range(3):
-        x += 0.1 * np.sin(2 * np.pi * rng.uniform(55, 4000) * t + rng.uniform(0, 2 * np.pi))
-    x += rng.uniform(-1e-3, 1e-3, n)
-    return x.astype(np.float32)
-
-
-def rms(a, b):
-    return float(np.sqrt(np.mean((np.asarray(a, np.float64) - np.asarray(b, np.float64)) ** 2)))
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def oracle_stream(x, N, hop_div, effect, scale, K):
-    hop = N // hop_div
-    xp = np.concatenate([np.zeros(N - hop, np.float32), x[:K * hop]])
-    return xp, pvref.std_process(xp, N, hop_div, ord(effect), scale, frames=K)
 
 
 @pytest.mark.parametrize("N,hop_div,effect,scale,per_push", [
@@ -59,7 +33,7 @@ def test_rt_stream_matches_oracle(cuda, N, hop_div, effect, scale, per_push):
     hs = rt.outHopSize
     spec = torch.zeros((1, per_push, rt.spec_stride, 2), dtype=torch.float32, device="cuda")
     outs, phases = [], []
-    xd = dev(x)
+    xd = to_dev(x)
     for j in range(K // per_push):
         o = rt.push(xd[j * per_push * hop:(j + 1) * per_push * hop], spec=spec)
         outs.append(o.cpu().numpy()[0])
@@ -84,12 +58,12 @@ def test_rt_many_channels_and_batch_equivalence(cuda):
     hop = N // hop_div
     xs = np.stack([synth(K * hop, 100 + c) for c in range(C)])
     rt = RealTimeVocoder(N, PITCH_SHIFT, 1.5, hop_div, channels=C)
-    xd = dev(xs)
+    xd = to_dev(xs)
     g = np.concatenate([rt.push(xd[:, j * hop:(j + 1) * hop].contiguous()).cpu().numpy()
                         for j in range(K)], axis=1)
     xp = np.concatenate([np.zeros((C, N - hop), np.float32), xs], axis=1)
     pv = PhaseVocoder(N, PITCH_SHIFT, 1.5, hop_div, mode=STANDARD, max_channels=C, max_frames=K)
-    out, _ = pv.process(dev(xp), frames=K)
+    out, _ = pv.process(to_dev(xp), frames=K)
     b = out.cpu().numpy()[:, :K * hop]
     assert np.max(np.abs(g - b)) <= 1e-6
     for c in (0, 77, 255):
@@ -108,7 +82,7 @@ def test_rt_graph_callback_equals_push_and_reset(cuda, monkeypatch, launch):
     a = RealTimeVocoder(N, PITCH_SHIFT, 2.0, hop_div, channels=C)
     b = RealTimeVocoder(N, PITCH_SHIFT, 2.0, hop_div, channels=C)
     b.capture(1)
-    xd = dev(xs)
+    xd = to_dev(xs)
     pa, pb = [], []
     for j in range(K):
         pa.append(a.push(xd[:, j * hop:(j + 1) * hop].contiguous()).cpu().numpy())

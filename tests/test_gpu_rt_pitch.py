@@ -9,10 +9,11 @@ import pytest
 
 import pvref
 import rt_pitch_ref as rp
+from gpu_helpers import RMS_TOL, status_of, to_dev
 from phase_lock_ref import chirp, mean_envelope, std_process_lock
 from pvamd import PITCH_SHIFT, STANDARD, TIME_SHIFT, PhaseVocoder, RealTimeVocoder, _lib
 from pvamd._lib import PVError
-from test_gpu_rt import RMS_TOL, dev, rms, synth
+from signals import rms, synth
 
 pytestmark = pytest.mark.gpu
 
@@ -30,7 +31,7 @@ def prefixed(x, N, hop):
 def pitch_stream(rt, xs, per_push, spec=None, phases=None):
     """xs [C, K hop] pushed per_push frames at a time -> the emitted stream [C, K hop]"""
     n = per_push * rt.hopSize
-    xd = dev(xs)
+    xd = to_dev(xs)
     outs = []
     for j in range(xs.shape[1] // n):
         outs.append(rt.pitch_push(xd[:, j * n:(j + 1) * n].contiguous(), spec=spec).cpu().numpy())
@@ -83,12 +84,12 @@ def test_locked_push_matches_batched_and_reference(cuda):
     xs = signal(K * hop, 5200, Cn)
     rt = RealTimeVocoder(N, TIME_SHIFT, scale, hop_div, channels=Cn, phase_lock=True)
     hs = rt.outHopSize
-    xd = dev(xs)
+    xd = to_dev(xs)
     g = np.concatenate([rt.push(xd[:, j * hop:(j + 1) * hop].contiguous()).cpu().numpy() for j in range(K)], axis=1)
     assert g.shape == (Cn, K * hs)
     xp = prefixed(xs, N, hop)
     pv = PhaseVocoder(N, TIME_SHIFT, scale, hop_div, mode=STANDARD, max_channels=Cn, max_frames=K, phase_lock=True)
-    out, _ = pv.process(dev(xp), frames=K)
+    out, _ = pv.process(to_dev(xp), frames=K)
     b = out.cpu().numpy()[:, :K * hs]
     d = float(np.max(np.abs(g - b)))
     print(f"locked push - batched locked process: max abs {d:.3e}")
@@ -151,7 +152,7 @@ def test_scale_one_is_push(cuda, lock):
     b = RealTimeVocoder(N, TIME_SHIFT, 1.0, hop_div, channels=C, phase_lock=lock)
     b.reserve_pitch(0, max_frames=2)
     assert b.pitch_latency == 0
-    xd = dev(xs)
+    xd = to_dev(xs)
     want = np.concatenate([a.push(xd[:, j * 2 * hop:(j + 1) * 2 * hop].contiguous()).cpu().numpy()
                            for j in range(K // 2)], axis=1)
     got = pitch_stream(b, xs, 2)
@@ -176,12 +177,6 @@ def test_locked_rt_pitch_keeps_a_chirps_amplitude(cuda):
     assert abs(e[0] - rp.RT_CHIRP_LOCKED) <= 1e-3
     assert abs(e[1] - rp.RT_CHIRP_UNLOCKED) <= 1e-3
     assert e[0] - e[1] >= (rp.RT_CHIRP_LOCKED - rp.RT_CHIRP_UNLOCKED) - 2e-3
-
-
-def status_of(fn):
-    with pytest.raises(PVError) as e:
-        fn()
-    return e.value.status
 
 
 def test_refusals(cuda):

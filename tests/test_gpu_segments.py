@@ -7,30 +7,11 @@ import numpy as np
 import pytest
 
 import pvref
+from gpu_helpers import RMS_TOL, free_port, run_segments, to_dev
 from pvamd import PITCH_SHIFT, STANDARD, TIME_SHIFT, PhaseVocoder
-from pvamd.dist import assemble_segments, frame_segments
-from test_gpu_parity import RMS_TOL, rms, synth, to_dev
+from signals import rms, synth
 
 pytestmark = pytest.mark.gpu
-
-
-def run_segments(pv, x, nseg):
-    import torch
-    xd = to_dev(x) if not isinstance(x, torch.Tensor) else x
-    xd = xd.unsqueeze(0) if xd.dim() == 1 else xd
-    n = xd.shape[1]
-    total = pv.num_frames(n)
-    hop = pv.hopSize
-    sums, blocks, firsts = [], [], []
-    for f0, nf in frame_segments(total, nseg):
-        if nf == 0:
-            continue
-        spec = pv.analysis(xd[:, f0 * hop:], frames=nf, n_samples=n - f0 * hop)
-        before = torch.stack(sums).contiguous() if sums else None
-        blocks.append(pv.segment_resynthesis(spec, f0, before, frames=nf))
-        sums.append(pv.segment_summary(spec, nf))
-        firsts.append(f0)
-    return assemble_segments(blocks, firsts, pv.outHopSize, pv.output_length(total))
 
 
 @pytest.mark.parametrize("N,hop_div,effect,scale,nseg", [
@@ -85,10 +66,9 @@ def test_two_rank_stream_segments(cuda):
     import os
     import subprocess
     import sys
-    from test_gpu_dist import _free_port
     here = os.path.dirname(os.path.abspath(__file__))
     world, n = 2, 120000
-    port = _free_port()
+    port = free_port()
     procs = []
     for r in range(world):
         env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK="0",

@@ -9,20 +9,15 @@ of fp32 denormals, as the 10 channels of one call per geometry.
   - an input scaled by 2^k gives the same phases and an exactly scaled output, bit for bit
     (no oracle, no tolerance): it fails on any hidden absolute constant.
 """
-import functools
-
 import numpy as np
 import pytest
 
 import pvref
+from gpu_helpers import ZOO_SAMPLES, oracle_stream, to_dev, zoo_input, zoo_reference
 from pvamd import PITCH_SHIFT, REF_COMPAT, STANDARD, TIME_SHIFT, PhaseVocoder, RealTimeVocoder
 from signals import ZOO_NAMES, assert_hop_parity, zoo_rows
-from test_gpu_parity import to_dev
-from test_gpu_rt import oracle_stream
 
 pytestmark = pytest.mark.gpu
-
-N_SAMPLES = 12001  # the last frame is ragged
 
 T, P = TIME_SHIFT, PITCH_SHIFT
 GEOMETRIES = [
@@ -54,27 +49,8 @@ def _id(v):
     return f"{N}-{hd}-{eff}-{sc}" + (f"-{env[0]}={env[1]}" if env else "")
 
 
-@functools.lru_cache(maxsize=None)
-def _rows(n, N):
-    xs = zoo_rows(n, N)
-    xs.setflags(write=False)
-    return xs
-
-
-@functools.lru_cache(maxsize=None)
-def _reference(N, hop_div, effect, scale):
-    """(oracle fp64 outputs per channel, port outputs [C, len], out hop): computed once per
-    geometry and shared, read-only"""
-    xs = _rows(N_SAMPLES, N)
-    refs = [pvref.std_process(x, N, hop_div, ord(effect), scale) for x in xs]
-    port, _ = pvref.port_std_process_batch(xs, N, hop_div, ord(effect), scale)
-    for a in refs + [port]:
-        a.setflags(write=False)
-    return refs, port, pvref.out_hop(N, hop_div, ord(effect), scale)
-
-
 def _vocoder(N, hop_div, effect, scale, C, **kw):
-    frames = pvref.num_frames(N_SAMPLES, N // hop_div)
+    frames = pvref.num_frames(ZOO_SAMPLES, N // hop_div)
     return PhaseVocoder(N, effect, scale, hop_div, mode=STANDARD, max_channels=C, max_frames=frames, **kw)
 
 
@@ -107,10 +83,10 @@ def _check_analysis(spec, xs, N, hop, frames, what, names, normal_only=False):
 def _spectra(N, hop_div, effect, scale):
     """the analysis kernel's rows (pv_analysis) and the rows pv_process returns (the single
     launch's own analysis for geometries 5, 9, 11 and 12)"""
-    xs = _rows(N_SAMPLES, N)
+    xs = zoo_input(ZOO_SAMPLES, N)
     pv = _vocoder(N, hop_div, effect, scale, len(xs))
     xd = to_dev(xs)
-    return xs, pv.num_frames(N_SAMPLES), (("analysis", pv.analysis(xd)), ("process", pv.process(xd)[1]))
+    return xs, pv.num_frames(ZOO_SAMPLES), (("analysis", pv.analysis(xd)), ("process", pv.process(xd)[1]))
 
 
 @pytest.mark.parametrize("N,hop_div,effect,scale", GEOMETRIES, ids=[_id((g, None)) for g in GEOMETRIES])
@@ -148,7 +124,7 @@ def test_zoo_process_per_hop(cuda, monkeypatch, variant):
     (N, hop_div, effect, scale), env = variant
     if env:
         monkeypatch.setenv(*env)
-    xs = _rows(N_SAMPLES, N)
+    xs = zoo_input(ZOO_SAMPLES, N)
     pv = _vocoder(N, hop_div, effect, scale, len(xs))
     if env and env[0] == "PV_RUN_FRAMES":
         assert pv.frames_per_run == int(env[1])
@@ -158,7 +134,7 @@ def test_zoo_process_per_hop(cuda, monkeypatch, variant):
         assert bool(pv.single_launch) == (variant[0] in SINGLE_LAUNCH)
     out, _ = pv.process(to_dev(xs))
     g = out.cpu().numpy()
-    refs, port, hs = _reference(N, hop_div, effect, scale)
+    refs, port, hs = zoo_reference(N, hop_div, effect, scale)
     assert hs == pv.outHopSize
     assert np.isfinite(g).all()
     for c, name in enumerate(ZOO_NAMES):
@@ -171,7 +147,7 @@ def test_zoo_process_per_hop(cuda, monkeypatch, variant):
 def test_zoo_real_time(cuda, N, hop_div, effect, scale, K):
     """the zoo as the 10 channels of a real-time stream pushed in random blocks of 1 .. 4 hops"""
     hop = N // hop_div
-    xs = _rows(K * hop, N)
+    xs = zoo_input(K * hop, N)
     rt = RealTimeVocoder(N, effect, scale, hop_div, channels=len(xs))
     hs = rt.outHopSize
     xd = to_dev(xs)
@@ -196,9 +172,9 @@ def test_zoo_ref_compat(cuda, N, hop_div):
     """REF_COMPAT on the signals without exactly-zero bins (atanf(0/0) is the reference's NaN
     behaviour, tests/test_gpu_dropin.py), the fp32 compat port as the yardstick"""
     names = ("noise_fs", "square", "synth")
-    xs = zoo_rows(N_SAMPLES, N, names)
+    xs = zoo_rows(ZOO_SAMPLES, N, names)
     pv = PhaseVocoder(N, TIME_SHIFT, 1.0, hop_div, mode=REF_COMPAT, max_channels=len(xs),
-                      max_frames=pvref.num_frames(N_SAMPLES, N // hop_div))
+                      max_frames=pvref.num_frames(ZOO_SAMPLES, N // hop_div))
     out, _ = pv.process(to_dev(xs))
     g = out.cpu().numpy()
     port, _ = pvref.port_compat_process_batch(xs, N, hop_div)
@@ -241,9 +217,9 @@ def _assert_scaled(base, got, k, what):
 def test_power_of_two_scaling_is_exact(cuda, N, hop_div, effect, scale, lock, k):
     """process(x * 2^k) against process(x): atan2 and the unwrap decisions see the same
     ratios, and the synthesis is linear in the magnitudes"""
-    xs = zoo_rows(N_SAMPLES, N, SCALED)
+    xs = zoo_rows(ZOO_SAMPLES, N, SCALED)
     pv = _vocoder(N, hop_div, effect, scale, len(xs), phase_lock=lock)
-    frames = pv.num_frames(N_SAMPLES)
+    frames = pv.num_frames(ZOO_SAMPLES)
     out0, spec0 = pv.process(to_dev(xs))
     out0, spec0 = out0.cpu().numpy(), spec0.cpu().numpy()[:, :frames, :N // 2 + 1]
     out1, spec1 = pv.process(to_dev(_scaled(xs, k)))

@@ -6,20 +6,22 @@ frames in runs of 8 (rate 0.73: 81 output frames, 11 runs, 3 workgroups, the las
 16 (PV_RUN_FRAMES).  The phases are the same integers on both sides, so the project's RMS_TOL
 holds as for every other synthesis mode with this sincos, FFT and overlap-add."""
 import ctypes
+import functools
 
 import numpy as np
 import pytest
 
 import pvref
 import timemap_ref as tm
+from gpu_helpers import (MAP_INPUTS, RMS_TOL, channel_errors, make_vocoder, status_of, stretch_inputs, to_dev,
+                         write_pcm16)
 from pvamd import PITCH_SHIFT, REF_COMPAT, STANDARD, TIME_SHIFT, PhaseVocoder, _lib, rate_map
-from pvamd._lib import PVError
-from test_gpu_parity import RMS_TOL, rms, synth, to_dev
+from signals import rms, synth
 
 pytestmark = pytest.mark.gpu
 
 C = 3
-FRAMES = 60
+FRAMES = MAP_INPUTS["frames"]
 MAX_FRAMES = 96
 
 GEOMETRIES = [
@@ -42,28 +44,17 @@ MAPS = {
 }
 
 
-def inputs(N, hop_div):
-    hop = N // hop_div
-    n = FRAMES * hop + 13  # not a multiple of the hop
-    assert pvref.num_frames(n, hop) == FRAMES
-    return np.stack([synth(n, 8100 + 11 * c + N) for c in range(C)])
+inputs = functools.partial(stretch_inputs, **MAP_INPUTS, channels=C)
 
 
 def make(monkeypatch, N, hop_div, F=8, **kw):
-    monkeypatch.setenv("PV_RUN_FRAMES", str(F))
-    pv = PhaseVocoder(N, TIME_SHIFT, 1.0, hop_div, mode=STANDARD, max_channels=C, max_frames=MAX_FRAMES, **kw)
-    assert pv.frames_per_run == F and pv.outHopSize == pv.hopSize
+    pv = make_vocoder(monkeypatch, N, hop_div, TIME_SHIFT, 1.0, F, max_frames=MAX_FRAMES, channels=C, **kw)
+    assert pv.outHopSize == pv.hopSize
     return pv
 
 
 def check_against_reference(out, xs, N, hop_div, pos, lock, what):
-    g = out.cpu().numpy()
-    assert np.isfinite(g).all()
-    worst = 0.0
-    for c in range(xs.shape[0]):
-        ref = tm.cached(xs[c], N, hop_div, pos, lock, FRAMES)
-        assert g[c].shape == ref.shape
-        worst = max(worst, rms(g[c], ref))
+    worst = max(channel_errors(out, lambda c: tm.cached(xs[c], N, hop_div, pos, lock, FRAMES), xs.shape[0]))
     print(f"N={N} hop_div={hop_div} lock={lock} {what} ({len(pos)} output frames): rms {worst:.3e}")
     assert worst <= RMS_TOL, f"{what}: rms {worst}"
 
@@ -210,7 +201,6 @@ def test_pv_main_rate(cuda, tmp_path):
     import subprocess
 
     from conftest import GOLDEN, ROOT
-    from test_gpu_dropin import write_pcm16
     pv_main = os.path.join(ROOT, "phase-vocoder_amd", "build", "pv_main")
     x = np.load(os.path.join(GOLDEN, "sine440_ch0_32768.npy"))[:16384].astype(np.float32)
     wav_in, dump = str(tmp_path / "in.wav"), str(tmp_path / "o.f32")
@@ -229,15 +219,6 @@ def test_pv_main_rate(cuda, tmp_path):
     r = subprocess.run([pv_main, wav_in, "p", str(tmp_path / "o2.wav"), *args], capture_output=True, text=True,
                        timeout=300)
     assert r.returncode == 1 and "--rate" in r.stderr
-
-
-def status_of(fn):
-    try:
-        fn()
-    except PVError as e:
-        assert len(str(e)) > 0
-        return e.status
-    return _lib.PV_OK
 
 
 def test_timemap_refusals(cuda):

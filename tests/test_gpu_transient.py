@@ -19,10 +19,10 @@ import pytest
 
 import pvref
 import transient_ref as T
+from gpu_helpers import RMS_TOL, channel_errors, make_vocoder, status_of, stretch_inputs, to_dev
 from pvamd import PITCH_SHIFT, REF_COMPAT, STANDARD, TIME_SHIFT, PhaseVocoder, _lib
-from pvamd._lib import PVError
 from resample_ref import resample as resample_ref
-from test_gpu_parity import RMS_TOL, rms, synth, to_dev
+from signals import rms, synth
 
 pytestmark = pytest.mark.gpu
 
@@ -50,26 +50,16 @@ def flags_array(frames=FRAMES):
 
 
 def inputs(N, hop_div):
-    hop = N // hop_div
-    n = FRAMES * hop + 13  # not a multiple of the hop
-    assert pvref.num_frames(n, hop) == FRAMES
-    return np.stack([synth(n, 7300 + 11 * c + N) for c in range(C)])
+    return stretch_inputs(N, hop_div, seed0=7300, seed_step=11, frames=FRAMES, channels=C)
 
 
 def make(monkeypatch, N, hop_div, scale, F=8, **kw):
-    monkeypatch.setenv("PV_RUN_FRAMES", str(F))
-    pv = PhaseVocoder(N, TIME_SHIFT, scale, hop_div, mode=STANDARD, max_channels=C, max_frames=FRAMES + 4, **kw)
-    assert pv.frames_per_run == F
-    return pv
+    return make_vocoder(monkeypatch, N, hop_div, TIME_SHIFT, scale, F, max_frames=FRAMES + 4, channels=C, **kw)
 
 
 def check_against_reference(out, xs, N, hop_div, scale, lock, fl):
-    g = out.cpu().numpy()
-    assert np.isfinite(g).all()
-    for c in range(xs.shape[0]):
-        ref = T.cached(xs[c], N, hop_div, scale, lock, fl[c])
-        assert g[c].shape == ref.shape
-        err = rms(g[c], ref)
+    errs = channel_errors(out, lambda c: T.cached(xs[c], N, hop_div, scale, lock, fl[c]), xs.shape[0])
+    for c, err in enumerate(errs):
         print(f"N={N} hop_div={hop_div} scale={scale} lock={lock} channel {c}: rms {err:.3e}")
         assert err <= RMS_TOL, f"channel {c}: rms {err}"
 
@@ -322,15 +312,6 @@ def test_flags_process_captures_into_a_graph(cuda, monkeypatch):
     g2.replay()
     torch.cuda.synchronize()
     assert torch.equal(out, ref)
-
-
-def status_of(fn):
-    try:
-        fn()
-    except PVError as e:
-        assert len(str(e)) > 0
-        return e.status
-    return _lib.PV_OK
 
 
 def test_transient_refusals(cuda):

@@ -4,23 +4,24 @@ locked or not, then the variable-rate resampling) against the reference composit
 n_in = 5003: several tiles of 1024 outputs and a partial one; block lengths below, across and above
 the tile; NaN-padded input rows an odd stride apart and sentinel-padded output rows throughout."""
 import ctypes
+import functools
 
 import numpy as np
 import pytest
 
 import pvref
 import varresample_ref as vr
+from gpu_helpers import (MAP_INPUTS, RMS_TOL, channel_errors, make_vocoder, run_padded, status_of, stretch_inputs,
+                         to_dev, to_dev_copy, write_pcm16)
 from pvamd import (PITCH_SHIFT, REF_COMPAT, STANDARD, TIME_SHIFT, PhaseVocoder, Resampler, VarResampler, _lib,
                    pitch_map_plan, rate_map)
-from pvamd._lib import PVError
-from test_gpu_parity import RMS_TOL, rms, synth, to_dev
+from signals import rms, synth
 
 pytestmark = pytest.mark.gpu
 
 C = 3
 N_IN = 5003
 PAD = 38  # rows n_in + 38 floats apart: the channels' rows start at different offsets in a 16-byte segment
-SENTINEL = -77.25
 ONE = 1 << 32
 
 _xs = {}
@@ -31,24 +32,6 @@ def signal(n=N_IN):
         _xs[n] = np.stack([synth(n, 4400 + 13 * c) for c in range(C)])
         _xs[n].setflags(write=False)
     return _xs[n]
-
-
-def padded_input(xs, pad=PAD):
-    import torch
-    buf = torch.full((xs.shape[0], xs.shape[1] + pad), float("nan"), dtype=torch.float32, device="cuda")
-    buf[:, :xs.shape[1]] = to_dev(np.array(xs))
-    return buf
-
-
-def run_padded(rs, xs, n_out):
-    """resample NaN-padded rows into sentinel-padded rows; the sentinel must survive"""
-    import torch
-    n = xs.shape[1]
-    buf = padded_input(xs)
-    ybuf = torch.full((xs.shape[0], n_out + 5), SENTINEL, dtype=torch.float32, device="cuda")
-    rs(buf[:, :n], n_out=n_out, out=ybuf[:, :n_out])
-    assert (ybuf[:, n_out:] == SENTINEL).all()
-    return ybuf[:, :n_out].cpu().numpy()
 
 
 def blocks_for(B, mean_ratio, cap=6000):
@@ -92,7 +75,7 @@ def test_varresample_parity(cuda, name, B, quality):
     assert rs.length == len(steps) * B
     n_out = rs.length - 7  # a multiple of neither the block nor the tile
     assert n_out % B and n_out % 1024
-    g = run_padded(rs, xs, n_out)
+    g = run_padded(rs, xs, PAD, n_out)
     assert np.isfinite(g).all()
     ref = vr.varresample(xs, steps, B, start, quality, n_out)
     assert g.shape == ref.shape
@@ -110,11 +93,11 @@ def test_constant_map_against_the_polyphase_kernel(cuda, p, q):
     xs = signal()
     poly = Resampler(p, q, 0)
     n_out = poly.length(N_IN)
-    want = poly(to_dev(np.array(xs))).cpu().numpy()
+    want = poly(to_dev_copy(xs)).cpu().numpy()
     B = 64
     rs = VarResampler(B, 0, max_blocks=-(-n_out // B))
     rs.set_map(np.full(-(-n_out // B), ONE * p // q, np.int64))
-    g = run_padded(rs, xs, n_out)
+    g = run_padded(rs, xs, PAD, n_out)
     for c in range(C):
         err = rms(g[c], want[c])
         print(f"{p}:{q} channel {c}: rms against k_resample {err:.3e}")
@@ -123,7 +106,7 @@ def test_constant_map_against_the_polyphase_kernel(cuda, p, q):
 
 def test_ratios_and_steps_set_the_same_map(cuda):
     import torch
-    xd = to_dev(np.array(signal()))
+    xd = to_dev_copy(signal())
     ratios = vr.vibrato(40)
     a, b = VarResampler(64, 0, max_blocks=40), VarResampler(64, 0, max_blocks=40)
     a.set_map(ratios)
@@ -134,7 +117,7 @@ def test_ratios_and_steps_set_the_same_map(cuda):
 def test_same_bits_again_alone_and_in_a_graph(cuda):
     import torch
     xs = signal()
-    xd = to_dev(np.array(xs))
+    xd = to_dev_copy(xs)
     steps, start = case_map("glide", 170)
     rs = VarResampler(170, 0, max_blocks=len(steps))
     rs.set_map(np.array(steps, np.int64), start)
@@ -161,24 +144,15 @@ def test_all_ones_map_is_the_shifted_copy(cuda):
     nb = -(-N_IN // B) + 2
     rs = VarResampler(B, 1, max_blocks=nb)
     rs.set_map(np.full(nb, ONE, np.int64), 7 * ONE)
-    g = run_padded(rs, xs, rs.length - 7)
+    g = run_padded(rs, xs, PAD, rs.length - 7)
     assert np.array_equal(g[:, :N_IN - 7], xs[:, 7:]) and not g[:, N_IN - 7:].any()
     rs.set_map(np.ones(nb))  # ratios 1.0, start 0
-    assert np.array_equal(run_padded(rs, xs, N_IN), xs)
+    assert np.array_equal(run_padded(rs, xs, PAD, N_IN), xs)
     # a later map with a fraction goes through the filter again
     rs.set_map(np.full(nb, ONE, np.int64), 7 * ONE + 1)
-    g = run_padded(rs, xs, N_IN - 7)
+    g = run_padded(rs, xs, PAD, N_IN - 7)
     ref = vr.varresample(xs, [ONE] * nb, B, 7 * ONE + 1, 1, N_IN - 7)
     assert not np.array_equal(g, xs[:, 7:]) and max(rms(g[c], ref[c]) for c in range(C)) <= RMS_TOL
-
-
-def status_of(fn):
-    try:
-        fn()
-    except PVError as e:
-        assert len(str(e)) > 0
-        return e.status
-    return _lib.PV_OK
 
 
 def test_varresampler_refusals(cuda):
@@ -219,16 +193,11 @@ def test_varresampler_refusals(cuda):
 
 
 # ------------------------------------------------------------------ pv_pitchmap_process
-FRAMES = 60
+FRAMES = MAP_INPUTS["frames"]
 MAX_FRAMES = 128
 GEOMETRIES = [(256, 4), (512, 3), (1024, 4)]
 
-
-def inputs(N, hop_div):
-    hop = N // hop_div
-    n = FRAMES * hop + 13
-    assert pvref.num_frames(n, hop) == FRAMES
-    return np.stack([synth(n, 8100 + 11 * c + N) for c in range(C)])  # test_gpu_timemap's inputs
+inputs = functools.partial(stretch_inputs, **MAP_INPUTS, channels=C)  # (the stretch's references are shared)
 
 
 def pitch_maps():
@@ -240,9 +209,8 @@ def pitch_maps():
 
 
 def make(monkeypatch, N, hop_div, **kw):
-    monkeypatch.setenv("PV_RUN_FRAMES", "8")
-    pv = PhaseVocoder(N, TIME_SHIFT, 1.0, hop_div, mode=STANDARD, max_channels=C, max_frames=MAX_FRAMES, **kw)
-    assert pv.frames_per_run == 8 and pv.outHopSize == pv.hopSize
+    pv = make_vocoder(monkeypatch, N, hop_div, TIME_SHIFT, 1.0, max_frames=MAX_FRAMES, channels=C, **kw)
+    assert pv.outHopSize == pv.hopSize
     return pv
 
 
@@ -262,13 +230,7 @@ def test_pitch_map_parity(cuda, monkeypatch, N, hop_div, lock):
         assert pv.time_map_frames == len(pos_s) and pv.pitch_map_output_length == pv.output_length(n)
         out, spec = pv.pitch_map_process(xd)
         assert out.shape == (C, n * hop + N - hop) and spec.shape[1] == FRAMES
-        g = out.cpu().numpy()
-        assert np.isfinite(g).all()
-        worst = 0.0
-        for c in range(C):
-            ref = vr.cached(xs[c], N, hop_div, pos_s, steps, lock, FRAMES, 0, n)
-            assert g[c].shape == ref.shape
-            worst = max(worst, rms(g[c], ref))
+        worst = max(channel_errors(out, lambda c: vr.cached(xs[c], N, hop_div, pos_s, steps, lock, FRAMES, 0, n), C))
         print(f"N={N} hop_div={hop_div} lock={lock} {what} ({n} frames, stretch {len(pos_s)}): rms {worst:.3e}")
         assert worst <= RMS_TOL, what
     pv.set_pitch_map(None)
@@ -401,7 +363,6 @@ def test_pv_main_pitch_glide(cuda, tmp_path):
     import subprocess
 
     from conftest import GOLDEN, ROOT
-    from test_gpu_dropin import write_pcm16
     pv_main = os.path.join(ROOT, "phase-vocoder_amd", "build", "pv_main")
     x = np.load(os.path.join(GOLDEN, "sine440_ch0_32768.npy"))[:16384].astype(np.float32)
     wav_in, dump = str(tmp_path / "in.wav"), str(tmp_path / "o.f32")

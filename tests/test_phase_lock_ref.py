@@ -12,24 +12,14 @@ import pytest
 import pvref
 from phase_lock_ref import chirp, mean_envelope, owners, peaks, std_process_lock
 from pvamd import _lib
+from signals import rms, synth
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 
 
-def rms(a, b):
-    return float(np.sqrt(np.mean((np.asarray(a, np.float64) - np.asarray(b, np.float64)) ** 2)))
-
-
-def tones(n, seed):
-    rng = np.random.default_rng(seed)
-    t = np.arange(n) / 44100.0
-    x = sum(0.1 * np.sin(2 * np.pi * rng.uniform(55, 4000) * t + rng.uniform(0, 2 * np.pi)) for _ in range(3))
-    return (x + rng.uniform(-1e-3, 1e-3, n)).astype(np.float32)
-
-
 @pytest.mark.parametrize("N,hop_div,scale", [(256, 4, 1.5), (512, 3, 0.75), (1024, 8, 1.37), (2048, 2, 0.5)])
 def test_unlocked_reference_is_the_oracle(N, hop_div, scale):
-    x = tones(12 * N + 37, 11)
+    x = synth(12 * N + 37, 11)
     ref = pvref.std_process(x, N, hop_div, ord("t"), scale)
     got = std_process_lock(x, N, hop_div, scale, lock=False)
     assert got.shape == ref.shape
@@ -72,7 +62,7 @@ def test_locking_keeps_a_chirps_amplitude():
 
 @pytest.mark.parametrize("N,hop_div", [(256, 2), (1024, 4)])
 def test_locking_is_the_identity_at_scale_one(N, hop_div):
-    x = tones(10 * N + 5, 12)
+    x = synth(10 * N + 5, 12)
     a = std_process_lock(x, N, hop_div, 1.0, lock=True)
     b = std_process_lock(x, N, hop_div, 1.0, lock=False)
     assert rms(a, b) <= 1e-12

@@ -16,23 +16,17 @@ from formant_ref import INPUT_PEAK, formant_peak, voice
 from phase_lock_ref import std_process_lock
 from pitch_formant_ref import std_process_warp, warp_map
 from pvamd import _lib
+from signals import synth
 
 CSRC = os.path.join(ROOT, "phase-vocoder_amd", "csrc")
 EXE = os.path.join(ROOT, "phase-vocoder_amd", "build", "tables_dump")
-
-
-def tones(n, seed):
-    rng = np.random.default_rng(seed)
-    t = np.arange(n) / 44100.0
-    x = sum(0.1 * np.sin(2 * np.pi * rng.uniform(55, 4000) * t + rng.uniform(0, 2 * np.pi)) for _ in range(3))
-    return (x + rng.uniform(-1e-3, 1e-3, n)).astype(np.float32)
 
 
 # ---------------------------------------------------------------- identities
 @pytest.mark.parametrize("lock", [False, True])
 @pytest.mark.parametrize("N,hop_div,scale", [(256, 4, 1.5), (512, 3, 0.75), (1024, 4, 0.5)])
 def test_order_zero_is_the_stretch_reference(N, hop_div, scale, lock):
-    x = tones(12 * N + 37, 31)
+    x = synth(12 * N + 37, 31)
     ref = std_process_lock(x, N, hop_div, scale, lock)
     got = std_process_warp(x, N, hop_div, scale, lock, 0)
     assert got.shape == ref.shape
@@ -45,7 +39,7 @@ def test_order_zero_is_the_stretch_reference(N, hop_div, scale, lock):
 @pytest.mark.parametrize("N,hop_div,order", [(256, 4, 1), (512, 2, 32), (1024, 4, 256)])
 def test_scale_one_is_the_plain_stretch(N, hop_div, order, lock):
     """out hop = hop: i_k = k, r_k = 0, the gain is exp(0) = 1"""
-    x = tones(10 * N + 5, 32)
+    x = synth(10 * N + 5, 32)
     a = std_process_warp(x, N, hop_div, 1.0, lock, order)
     b = std_process_warp(x, N, hop_div, 1.0, lock, 0)
     d = float(np.max(np.abs(a - b)))

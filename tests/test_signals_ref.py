@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import pvref
-from signals import PORT_CAP, ZOO_NAMES, assert_hop_parity, hop_errors, rms, zoo, zoo_rows
+from signals import PORT_CAP, ZOO_NAMES, assert_hop_parity, hop_errors, rms, synth, zoo, zoo_rows
 
 # (N, hop_div, effect, scale): the geometries of tests/test_gpu_signals.py
 GEOMETRIES = [
@@ -111,7 +111,6 @@ def test_oracle_power_of_two_scale_is_exact(N, hop_div, effect, scale, k):
 @pytest.fixture(scope="module")
 def case():
     """synth(40000, 31) at N = 1024, hop_div 4, stretch 0.5 (out hop 128): oracle and port"""
-    from test_gpu_parity import synth
     x = synth(40000, 31)
     ref = pvref.std_process(x, 1024, 4, ord("t"), 0.5)
     port, _ = pvref.port_std_process_batch(x[None], 1024, 4, ord("t"), 0.5, None, 1)

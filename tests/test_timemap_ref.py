@@ -12,24 +12,14 @@ from phase_lock_ref import chirp, mean_envelope
 from pvamd import _lib
 import pvamd
 import timemap_ref as tm
-
-
-def rms(a, b):
-    return float(np.sqrt(np.mean((np.asarray(a, np.float64) - np.asarray(b, np.float64)) ** 2)))
-
-
-def tones(n, seed):
-    rng = np.random.default_rng(seed)
-    t = np.arange(n) / 44100.0
-    x = sum(0.1 * np.sin(2 * np.pi * rng.uniform(55, 4000) * t + rng.uniform(0, 2 * np.pi)) for _ in range(3))
-    return (x + rng.uniform(-1e-3, 1e-3, n)).astype(np.float32)
+from signals import rms, synth
 
 
 @pytest.mark.parametrize("lock", [False, True])
 @pytest.mark.parametrize("N", [256, 512, 1024])
 def test_identity_map_is_the_oracles_scale_1_stretch(N, lock):
     hop_div = 4
-    x = tones(14 * N + 37, 21)
+    x = synth(14 * N + 37, 21)
     frames = pvref.num_frames(len(x), N // hop_div)
     ref = pvref.std_process(x, N, hop_div, ord("t"), 1.0)
     got = tm.timemap_process(x, N, hop_div, np.arange(frames, dtype=np.float64), lock)
@@ -42,7 +32,7 @@ def test_identity_map_is_the_oracles_scale_1_stretch(N, lock):
 @pytest.mark.parametrize("lock", [False, True])
 def test_identity_map_telescopes_to_the_analysis_phase(lock):
     N, hop = 256, 64
-    x = tones(40 * hop + 11, 4)
+    x = synth(40 * hop + 11, 4)
     frames = pvref.num_frames(len(x), hop)
     mag, ph = pvref.std_analysis(x, N, hop, frames)
     P = tm.phase_turns(ph)
@@ -54,7 +44,7 @@ def test_identity_map_telescopes_to_the_analysis_phase(lock):
 
 def test_runs_with_carries_give_the_sequential_sum():
     N, hop = 256, 64
-    x = tones(60 * hop + 200, 9)
+    x = synth(60 * hop + 200, 9)
     frames = pvref.num_frames(len(x), hop)
     _, ph = pvref.std_analysis(x, N, hop, frames)
     P = tm.phase_turns(ph)

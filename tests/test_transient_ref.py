@@ -13,27 +13,17 @@ import pytest
 import pvref
 from phase_lock_ref import std_process_lock
 from pvamd import _lib
+from signals import rms, synth
 from transient_ref import (DEFAULT_THRESHOLD, bursts, clear, click_flags, click_frames, clicks, compactness, pick,
                            std_process_reset, strengths)
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 
 
-def rms(a, b):
-    return float(np.sqrt(np.mean((np.asarray(a, np.float64) - np.asarray(b, np.float64)) ** 2)))
-
-
-def tones(n, seed):
-    rng = np.random.default_rng(seed)
-    t = np.arange(n) / 44100.0
-    x = sum(0.1 * np.sin(2 * np.pi * rng.uniform(55, 4000) * t + rng.uniform(0, 2 * np.pi)) for _ in range(3))
-    return (x + rng.uniform(-1e-3, 1e-3, n)).astype(np.float32)
-
-
 @pytest.mark.parametrize("lock", [False, True])
 @pytest.mark.parametrize("N,hop_div,scale", [(256, 4, 1.5), (512, 3, 0.75), (1024, 4, 0.5)])
 def test_without_flags_the_reference_is_the_phase_lock_reference(N, hop_div, scale, lock):
-    x = tones(12 * N + 37, 11)
+    x = synth(12 * N + 37, 11)
     ref = std_process_lock(x, N, hop_div, scale, lock)
     frames = pvref.num_frames(len(x), N // hop_div)
     for flags in (None, np.zeros(frames, np.uint8)):
@@ -45,7 +35,7 @@ def test_without_flags_the_reference_is_the_phase_lock_reference(N, hop_div, sca
 @pytest.mark.parametrize("lock", [False, True])
 def test_a_flagged_frames_spectrum_is_the_analysis_spectrum(lock):
     N, hop_div, scale = 256, 4, 1.5
-    x = tones(30 * 64 + 5, 3)
+    x = synth(30 * 64 + 5, 3)
     frames = pvref.num_frames(len(x), N // hop_div)
     flags = np.zeros(frames, np.uint8)
     flags[[0, 7, 19]] = 1  # (frame 0's flag is ignored)
@@ -67,7 +57,7 @@ def test_a_flag_changes_nothing_before_its_frame_and_has_no_run_boundaries():
     changes no sample before t0's first output position.  (Stated here so that the GPU test,
     whose kernels do have runs, mirrors it: tests/test_gpu_transient.py.)"""
     N, hop_div, scale = 256, 4, 1.5
-    x = tones(40 * 64 + 5, 4)
+    x = synth(40 * 64 + 5, 4)
     hs = pvref.out_hop(N, hop_div, ord("t"), scale)
     frames = pvref.num_frames(len(x), N // hop_div)
     plain = std_process_reset(x, N, hop_div, scale, False, None)

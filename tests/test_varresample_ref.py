@@ -13,10 +13,7 @@ import timemap_ref as tm
 import varresample_ref as vr
 import pvamd
 from pvamd import _lib
-
-
-def rms(a, b):
-    return float(np.sqrt(np.mean((np.asarray(a, np.float64) - np.asarray(b, np.float64)) ** 2)))
+from signals import rms
 
 
 # ------------------------------------------------------------------ pinned to resample_ref

@@ -13,12 +13,11 @@ analysis hop:
 With the identity map it reproduces pvref.std_process at scale 1 (tests/test_timemap_ref.py),
 which is what makes it a yardstick for the other maps.
 """
-import functools
-
 import numpy as np
 
 import pvref
 from phase_lock_ref import owners, peaks
+from ref_cache import array, memo
 
 TWO_PI = 2.0 * np.pi
 INV_2PI = np.float32(float.fromhex("0x1.45f306p-3"))  # kInv2Pi (pv_device.hpp)
@@ -121,22 +120,10 @@ def timemap_process(x, N, hop_div, pos, lock, frames=None):
     return out
 
 
-_inputs = {}
-
-
-@functools.lru_cache(maxsize=None)
-def _cached(key, N, hop_div, pkey, lock, frames):
-    return timemap_process(_inputs[key], N, hop_div, np.frombuffer(pkey, np.float64), lock, frames)
-
-
+@memo(x=array(np.float32), pos=array(np.float64), lock=bool)
 def cached(x, N, hop_div, pos, lock, frames=None):
     """timemap_process, computed once per (input, configuration, map) and shared read-only."""
-    x = np.ascontiguousarray(x, np.float32)
-    key = hash(x.tobytes())
-    _inputs.setdefault(key, x)
-    out = _cached(key, N, hop_div, np.ascontiguousarray(pos, np.float64).tobytes(), bool(lock), frames)
-    out.setflags(write=False)
-    return out
+    return timemap_process(x, N, hop_div, pos, lock, frames)
 
 
 # ---------------------------------------------------------------- maps

@@ -14,12 +14,11 @@ Detector: rise[t] = sum_k max(0, mag_t[k] - mag_{t-1}[k]) (mag_{-1} = 0), tot[t]
 (a NaN magnitude adds 0 to both); flag[t] = t >= 1 and rise[t] > thr tot[t] and rise[t] >
 rise[t-1] and rise[t] >= rise[t+1] (rise[frames] = 0).
 """
-import functools
-
 import numpy as np
 
 import pvref
 from phase_lock_ref import owners, peaks
+from ref_cache import array, memo
 
 TWO_PI = 2.0 * np.pi
 DEFAULT_THRESHOLD = 0.3  # PV_TRANSIENT_DEFAULT_THRESHOLD (include/pv.h)
@@ -74,23 +73,10 @@ def std_process_reset(x, N, hop_div, scale, lock, flags, frames=None, spectra=No
     return out
 
 
-_inputs = {}
-
-
-@functools.lru_cache(maxsize=None)
-def _cached(key, N, hop_div, scale, lock, fkey, frames):
-    return std_process_reset(_inputs[key], N, hop_div, scale, lock, np.frombuffer(fkey, np.uint8), frames)
-
-
+@memo(x=array(np.float32), scale=float, lock=bool, flags=lambda f: (np.asarray(f) != 0).astype(np.uint8))
 def cached(x, N, hop_div, scale, lock, flags, frames=None):
     """std_process_reset, computed once per (input, configuration, flags) and shared read-only."""
-    x = np.ascontiguousarray(x, np.float32)
-    key = hash(x.tobytes())
-    _inputs.setdefault(key, x)
-    fkey = (np.asarray(flags) != 0).astype(np.uint8).tobytes()
-    out = _cached(key, N, hop_div, float(scale), bool(lock), fkey, frames)
-    out.setflags(write=False)
-    return out
+    return std_process_reset(x, N, hop_div, scale, lock, flags, frames)
 
 
 # ---------------------------------------------------------------- detector

@@ -14,11 +14,11 @@ The pitch map: per final output frame u < n a position pos[u] (the tempo curve) 
 ratio[u]; `plan` gives the time map pos_s of the stretch and the steps of the resampling that
 follows it, `pitchmap_process` is timemap_ref.timemap_process(pos_s), then `varresample`.
 """
-import functools
 import math
 
 import numpy as np
 
+from ref_cache import array, memo
 from resample_ref import PRESETS
 
 ONE = 1 << 32
@@ -134,24 +134,10 @@ def pitchmap_process(x, N, hop_div, pos_s, steps, lock, frames=None, quality=0, 
     return varresample(mid, steps, hop, 0, quality, n_out)
 
 
-_inputs = {}
-
-
-@functools.lru_cache(maxsize=None)
-def _cached(key, N, hop_div, pkey, skey, lock, frames, quality, n):
-    return pitchmap_process(_inputs[key], N, hop_div, np.frombuffer(pkey, np.float64), list(skey), lock, frames,
-                            quality, n)
-
-
+@memo(x=array(np.float32), pos_s=array(np.float64), steps=array(np.int64), lock=bool)
 def cached(x, N, hop_div, pos_s, steps, lock, frames=None, quality=0, n=None):
     """pitchmap_process, computed once per (input, configuration, plan) and shared read-only."""
-    x = np.ascontiguousarray(x, np.float32)
-    key = hash(x.tobytes())
-    _inputs.setdefault(key, x)
-    out = _cached(key, N, hop_div, np.ascontiguousarray(pos_s, np.float64).tobytes(), tuple(int(d) for d in steps),
-                  bool(lock), frames, quality, n)
-    out.setflags(write=False)
-    return out
+    return pitchmap_process(x, N, hop_div, pos_s, steps, lock, frames, quality, n)
 
 
 # ---------------------------------------------------------------- maps
