@@ -87,7 +87,10 @@ extern "C" {
                                 pv_varresampler_* / pv_varresample / pv_varresample_steps /
                                 pv_varresample_length, pv_pitchmap_plan / pv_pitchmap_set /
                                 pv_pitchmap_output_length / pv_pitchmap_process,
-                                pv_resident_min_channels, pv_pitch_track / pv_pitch_correct_plan) */
+                                pv_resident_min_channels, pv_pitch_track / pv_pitch_correct_plan,
+                                pv_timemap_set_channels / pv_timemap_channels,
+                                pv_varresampler_set_maps / pv_varresample_map_channels,
+                                pv_pitchmap_set_channels) */
 
 typedef struct pv_handle pv_handle;
 
@@ -479,7 +482,7 @@ pv_status pv_onset_strength(pv_handle* h, const pv_float2* spec, long long ld_sp
 
 /* Time-map stretch: an arbitrary, time-varying playback rate.  Output frame
  * u < n_out is built at the fractional analysis position pos[u] (in frames; one map for all
- * channels of a call) with the synthesis hop equal to the analysis hop, so a tempo curve, a ratio
+ * channels of a call unless set per channel, pv_timemap_set_channels below) with the synthesis hop equal to the analysis hop, so a tempo curve, a ratio
  * that is no multiple of 1/hop, a freeze (pos constant), a scrub and a reverse (pos decreasing)
  * are all maps.  The handle: STANDARD + PV_TIME_SHIFT with out_hop == hop (scale 1), natural or
  * packed rows, n_samps in [256, 2048]; the map replaces the scale.
@@ -518,10 +521,32 @@ pv_status pv_onset_strength(pv_handle* h, const pv_float2* spec, long long ld_sp
  *   REF_COMPAT handle, a PV_PITCH_SHIFT handle, out_hop != hop: PV_ERR_UNSUPPORTED; process before
  *   a successful set, frames < 1 with channels > 0, max i_u > frames - 1, the transient mode not
  *   OFF, pv_pitch_set_formant on: PV_ERR_ARG.
+ * A map per channel.  pv_timemap_set_channels: pos[c*ld_pos + u] is channel c's
+ *   position for output frame u, u < counts[c] (counts in [1, n_out]; NULL: n_out for every
+ *   channel; the entries from counts[c] on are not read).  Everything above holds per channel with
+ *   its own map: Phi(0) = P(i_0) of the channel's own i_0, the same integer scan, the same
+ *   magnitudes, pv_set_phase_lock composes.  Output frames u >= counts[c] of channel c contribute
+ *   nothing: its row is pv_output_length(h, n_out) samples like every other, and its samples from
+ *   pv_output_length(h, counts[c]) on are 0; below that it is, bit for bit, the row of
+ *   pv_timemap_set(pos + c*ld_pos, counts[c]) and a call of that channel alone.  1 <= channels <=
+ *   max_channels, 1 <= n_out <= max_frames, ld_pos >= n_out with more than one channel;
+ *   pv_timemap_frames then reads n_out and pv_timemap_channels `channels`.  pv_timemap_process
+ *   takes channels <= pv_timemap_channels(h), channel c with map c; "max i_u <= frames - 1" is
+ *   checked over the call's channels and their counted frames.  A setup call, ordered like
+ *   pv_timemap_set; the first one grows the map to max_channels x max_frames entries of 8 bytes
+ *   (PV_ERR_NOMEM: the previous state stays).  pv_timemap_set (a shared map, or the clear) replaces
+ *   a map per channel and the other way round; either turns a pitch map off.
+ *   pv_timemap_channels: 0 for NULL, without a map, or with the shared one.
+ *   PV_ERR_ARG, with the channel named in pv_last_error where one is at fault: NULL positions,
+ *   channels, n_out or a count out of range, ld_pos < n_out, a position pv_timemap_split refuses
+ *   among a channel's counted ones; at process time more channels than the map has.
  * pv_process and every other entry point are unchanged by a map. */
 pv_status pv_timemap_split(const double* pos, int n, int* idx, float* frac);
 pv_status pv_timemap_set(pv_handle* h, const double* pos, int n_out);
+pv_status pv_timemap_set_channels(pv_handle* h, const double* pos, long long ld_pos,
+                                  const int* counts /* nullable */, int channels, int n_out);
 int pv_timemap_frames(const pv_handle* h);
+int pv_timemap_channels(const pv_handle* h);   /* 0: no map, or the shared one */
 pv_status pv_timemap_process(pv_handle* h, const float* x, long long ldx, long long n_samples, int channels,
                              int frames, pv_float2* spec, long long ld_spec, float* out, long long ldo,
                              void* stream);
@@ -556,12 +581,27 @@ pv_status pv_timemap_process(pv_handle* h, const float* x, long long ldx, long l
  *   block outside [16, 4096], max_blocks < 1; nblocks outside [1, max_blocks]; a step out of
  *   range; a negative start or positions past 2^62; pv_varresample before a map; n_out > length;
  *   x and y overlapping; ldx < n_in or ldy < n_out with more than one channel; a ratio that is
- *   not finite or outside [1/4, 4], or n <= 0. */
+ *   not finite or outside [1/4, 4], or n <= 0.
+ * Maps per channel.  pv_varresampler_set_maps: channel c starts at start[c] and
+ *   has the steps step[c*ld_step + b], b < nblocks (the same nblocks for every channel); the
+ *   validation, the records and the tile spans are pv_varresampler_set_map's per channel, and
+ *   channel c of pv_varresample is, bit for bit, what that shared map gives the channel alone.  A
+ *   channel whose steps are all 2^32 and whose start has no fraction is the shifted copy, whatever
+ *   the other channels are.  A setup call; it allocates or grows the channels' records (about 24
+ *   bytes per block and 16 per tile and channel; PV_ERR_NOMEM: the previous state stays).
+ *   pv_varresample then takes channels <= pv_varresample_map_channels(vr) (0 for NULL, without a
+ *   map, or with the shared one).  pv_varresampler_set_map replaces the maps per channel with the
+ *   shared one, and the other way round.  PV_ERR_ARG also on channels < 1, ld_step < nblocks with
+ *   more than one channel, and a call with more channels than the maps; the channel at fault is
+ *   named in pv_last_error. */
 typedef struct pv_varresampler pv_varresampler;
 pv_status pv_varresampler_create(int quality, int block, int max_blocks, int device, pv_varresampler** out);
 void pv_varresampler_destroy(pv_varresampler* vr);
 pv_status pv_varresample_steps(const double* ratio, int n, long long* step);
 pv_status pv_varresampler_set_map(pv_varresampler* vr, long long start, const long long* step, int nblocks);
+pv_status pv_varresampler_set_maps(pv_varresampler* vr, int channels, const long long* start /* [channels] */,
+                                   const long long* step, long long ld_step, int nblocks);
+int pv_varresample_map_channels(const pv_varresampler* vr);   /* 0: no map, or the shared one */
 long long pv_varresample_length(const pv_varresampler* vr);
 pv_status pv_varresample(pv_varresampler* vr, const float* x, long long ldx, long long n_in, int channels,
                          float* y, long long ldy, long long n_out, void* stream);
@@ -594,11 +634,24 @@ pv_status pv_varresample(pv_varresampler* vr, const float* x, long long ldx, lon
  *     refusals, plus PV_ERR_ARG without a pitch map.  Launches: pv_timemap_process's, then
  *     var_resample.  pv_set_phase_lock composes.  With ratio = 1 throughout it is
  *     pv_timemap_process of pos, bit for bit.
- * One map for all channels.  pv_rt, the harmoniser, the stream segments and the envelope warp
- * have no pitch map.  pv_process and every other entry point are unchanged by one. */
+ *   pv_pitchmap_set_channels: pos[c*ld_pos + u] and ratio[c*ld_ratio + u], u < n,
+ *     per channel c < channels <= max_channels.  The plan runs per channel; the stretch maps go in
+ *     as pv_timemap_set_channels installs them, with counts n_s[c] and n_out = max_c n_s[c] (a
+ *     channel whose n_s exceeds max_frames: PV_ERR_ARG, the channel named), the steps as
+ *     pv_varresampler_set_maps does.  pv_pitchmap_process then takes channels <=
+ *     pv_timemap_channels(h); channel c is, bit for bit, pv_pitchmap_set(pos + c*ld_pos, ratio +
+ *     c*ld_ratio, n) run on that channel alone (a shorter channel's stretched samples up to the
+ *     longest's length are exact zeros, which is what the resampler reads past a row's end), and
+ *     a channel at ratio 1 throughout is pv_timemap_process of its positions.  The clear, the
+ *     output length and the refusals are pv_pitchmap_set's.
+ * One map for all channels unless set per channel.  pv_rt, the harmoniser, the stream segments and
+ * the envelope warp have no pitch map.  pv_process and every other entry point are unchanged by
+ * one. */
 pv_status pv_pitchmap_plan(int n_samps, int hop, const double* pos, const double* ratio, int n, double* pos_s,
                            int cap_s, int* n_s, long long* step, int cap_steps, int* n_steps);
 pv_status pv_pitchmap_set(pv_handle* h, const double* pos, const double* ratio, int n, int quality);
+pv_status pv_pitchmap_set_channels(pv_handle* h, const double* pos, long long ld_pos, const double* ratio,
+                                   long long ld_ratio, int channels, int n, int quality);
 long long pv_pitchmap_output_length(const pv_handle* h);
 pv_status pv_pitchmap_process(pv_handle* h, const float* x, long long ldx, long long n_samples, int channels,
                               int frames, pv_float2* spec, long long ld_spec, float* out, long long ldo,
@@ -646,8 +699,9 @@ pv_status pv_pitchmap_process(pv_handle* h, const float* x, long long ldx, long 
  *   PV_ERR_ARG with a pv_last_error text: a NULL track, cfg or ratio, frames or n < 1,
  *   cfg->abi_version != PV_ABI_VERSION, a field of cfg outside its range, a position that is not
  *   finite.
- * One correction curve per call: one voice, or channels that share a voice, since pv_pitchmap_set
- * is one map for all channels.  pv_rt and pv_main have no tracker. */
+ * One correction curve per call: one voice, or channels that share a voice; a batch of voices is
+ * one call per channel's track and one pv_pitchmap_set_channels (pv_pitchmap_set is one map for
+ * all channels unless set per channel).  pv_rt and pv_main have no tracker. */
 #define PV_PITCH_TRACK_DEFAULT_KAPPA 0.9f
 typedef struct pv_pitch_correct {
     int abi_version;      /* = PV_ABI_VERSION */

@@ -1,6 +1,7 @@
 // pv_api_timemap.cpp — the time-map stretch of libpv (pv_timemap_*): the
 // host split of the map, the handle's map and scan buffers, and the launch sequence of
-// pv_timemap_process (analysis, map_sum, map_carry, synthesis_map, seam).
+// pv_timemap_process (analysis, map_sum, map_carry, synthesis_map, seam).  The map is one for all
+// channels (pv_timemap_set) or one per channel (pv_timemap_set_channels).
 #include <algorithm>
 #include <vector>
 
@@ -39,6 +40,25 @@ pv_status reserve(pv_handle* h) {
     h->d_map_sum = std::move(sum);
     h->d_map_carry = std::move(carry);
     h->d_map = std::move(map);
+    h->map_rows = 1;
+    return PV_OK;
+}
+
+// the first per-channel set: max_channels rows of max_frames entries and the channels' counts.
+// Allocated before anything of the handle's is touched: on PV_ERR_NOMEM the previous state stays
+// (the shared map's entries are not carried over: the caller's set replaces them).
+pv_status reserve_rows(pv_handle* h, const std::string& fn) {
+    const size_t C = (size_t)std::max(h->cfg.max_channels, 1), T = (size_t)std::max(h->cfg.max_frames, 1);
+    if (h->map_rows >= (long long)C && h->d_map_counts) return PV_OK;
+    DevBuf<pv::MapEntry> map;
+    DevBuf<int> counts;
+    if (map.alloc_zero(C * T) != hipSuccess || counts.alloc_zero(C) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(PV_ERR_NOMEM, fn + ": the channels' maps (max_channels x max_frames entries)");
+    }
+    h->d_map = std::move(map);
+    h->d_map_counts = std::move(counts);
+    h->map_rows = (long long)C;
     return PV_OK;
 }
 
@@ -52,6 +72,7 @@ pv_status timemap_set(const char* fn_, pv_handle* h, const double* pos, int n_ou
     if (!pos && n_out == 0) {  // clear (the calls enqueued before it have read their map)
         h->map_n = 0;
         h->map_imax = 0;
+        h->map_channels = h->map_counted = 0;
         return PV_OK;
     }
     if (!pos) return fail(PV_ERR_ARG, fn + ": null positions");
@@ -71,6 +92,55 @@ pv_status timemap_set(const char* fn_, pv_handle* h, const double* pos, int n_ou
     PV_HIP(hipDeviceSynchronize());
     h->map_n = n_out;
     h->map_imax = *std::max_element(idx.begin(), idx.end());
+    h->map_channels = h->map_counted = 0;  // the shared map replaces a map per channel
+    return PV_OK;
+}
+
+pv_status timemap_set_channels(const char* fn_, pv_handle* h, const double* pos, long long ld_pos, const int* counts,
+                               int channels, int n_out) {
+    const std::string fn(fn_);
+    pv_status st = check_handle(fn_, h);
+    if (st != PV_OK) return st;
+    if (!pos) return fail(PV_ERR_ARG, fn + ": null positions");
+    if (channels < 1 || channels > h->cfg.max_channels)
+        return fail(PV_ERR_ARG, fn + ": channels must be in [1, max_channels]");
+    if (n_out < 1 || n_out > h->cfg.max_frames)
+        return fail(PV_ERR_ARG, fn + ": n_out must be in [1, max_frames]");
+    if (channels > 1 && ld_pos < n_out) return fail(PV_ERR_ARG, fn + ": ld_pos < n_out");
+    const size_t T = (size_t)h->cfg.max_frames;
+    // rows of max_frames entries; past a channel's count its last entry repeated (valid rows
+    // whatever a kernel reads), zeros ({row 0, fraction 0}) past n_out
+    std::vector<pv::MapEntry> map((size_t)channels * T, pv::MapEntry{0, 0.0f});
+    std::vector<int> cnt((size_t)channels), imax((size_t)channels), idx((size_t)n_out);
+    std::vector<float> frac((size_t)n_out);
+    bool counted = false;
+    for (int c = 0; c < channels; ++c) {
+        const int n_c = counts ? counts[c] : n_out;
+        const std::string ch = " (channel " + std::to_string(c) + ")";
+        if (n_c < 1 || n_c > n_out) return fail(PV_ERR_ARG, fn + ": every count must be in [1, n_out]" + ch);
+        if (!timemap_split(pos + (long long)c * ld_pos, n_c, idx.data(), frac.data()))
+            return fail(PV_ERR_ARG, fn + ": every position must be finite, >= 0 and < 2^30" + ch);
+        pv::MapEntry* row = map.data() + (size_t)c * T;
+        for (int u = 0; u < n_out; ++u) {
+            const int v = std::min(u, n_c - 1);
+            row[u] = pv::MapEntry{idx[(size_t)v], frac[(size_t)v]};
+        }
+        cnt[(size_t)c] = n_c;
+        imax[(size_t)c] = *std::max_element(idx.begin(), idx.begin() + n_c);
+        counted = counted || n_c < n_out;
+    }
+    DeviceGuard g(h->cfg.device);
+    // ordered like pv_timemap_set
+    PV_HIP(hipDeviceSynchronize());
+    if ((st = reserve(h)) != PV_OK || (st = reserve_rows(h, fn)) != PV_OK) return st;
+    PV_HIP(hipMemcpy(h->d_map, map.data(), sizeof(pv::MapEntry) * map.size(), hipMemcpyHostToDevice));
+    PV_HIP(hipMemcpy(h->d_map_counts, cnt.data(), sizeof(int) * cnt.size(), hipMemcpyHostToDevice));
+    PV_HIP(hipDeviceSynchronize());
+    h->map_n = n_out;
+    h->map_imax_c = std::move(imax);
+    h->map_imax = *std::max_element(h->map_imax_c.begin(), h->map_imax_c.end());
+    h->map_channels = channels;
+    h->map_counted = counted ? 1 : 0;
     return PV_OK;
 }
 
@@ -82,8 +152,15 @@ pv_status timemap_check(const char* fn_, const pv_handle* h, const float* x, int
     if (h->pitch_formant)
         return fail(PV_ERR_ARG, fn + ": not while the envelope warp is on (pv_pitch_set_formant)");
     if (frames < 1) return fail(PV_ERR_ARG, fn + ": frames must be at least 1");
-    // every row the kernels read, i_u and (for i_u < frames - 1) i_u + 1, is an analysed one
-    if (h->map_imax > frames - 1)
+    // every row the kernels read, i_u and (for i_u < frames - 1) i_u + 1, is an analysed one: with
+    // a map per channel, of the call's channels and their counted frames
+    int imax = h->map_imax;
+    if (h->map_channels > 0) {
+        if (channels > h->map_channels)
+            return fail(PV_ERR_ARG, fn + ": more channels than the map has (pv_timemap_channels)");
+        imax = *std::max_element(h->map_imax_c.begin(), h->map_imax_c.begin() + channels);
+    }
+    if (imax > frames - 1)
         return fail(PV_ERR_ARG, fn + ": the map reads past the last analysed frame (max floor(pos) > frames - 1)");
     if (!x || !out) return fail(PV_ERR_ARG, "null x/out");
     if (channels > 1 && ldo < pv_output_length(h, h->map_n))
@@ -113,6 +190,8 @@ pv_status timemap_launch(const char* fn, pv_handle* h, const float* x, long long
     m.bins_pad = h->bins_pad;
     m.packed = h->packed;
     m.map = h->d_map;
+    m.ld_map = h->map_channels > 0 ? h->cfg.max_frames : 0;
+    m.counts = h->map_counted ? h->d_map_counts.p : nullptr;
     m.sum = h->d_map_sum;
     m.carry = h->d_map_carry;
     PV_LAUNCH(h, KMS, s, pv::launch_map_sum(channels, m, s));
@@ -124,7 +203,7 @@ pv_status timemap_launch(const char* fn, pv_handle* h, const float* x, long long
     p.q_pow2 = 1;
     p.p_mod = 0;
     p.inv_q = 1.0f;
-    pv::set_map_args(&p, pv::MapArgs{h->d_map, frames});
+    pv::set_map_args(&p, pv::MapArgs{h->d_map, frames, m.ld_map, m.counts});
     PV_LAUNCH(h, KSM, s, pv::launch_synthesis_map(h->L_syn, h->phase_lock, channels, p, s));
     return do_seam(h, channels, n_out, nullptr, 0, out, ldo, olen, s);
 }
@@ -153,7 +232,16 @@ pv_status pv_timemap_set(pv_handle* h, const double* pos, int n_out) {
     return st;
 }
 
+pv_status pv_timemap_set_channels(pv_handle* h, const double* pos, long long ld_pos, const int* counts, int channels,
+                                  int n_out) {
+    const pv_status st = timemap_set_channels("pv_timemap_set_channels", h, pos, ld_pos, counts, channels, n_out);
+    if (st == PV_OK) h->pmap_n = 0;  // (as pv_timemap_set: a pitch map is off)
+    return st;
+}
+
 int pv_timemap_frames(const pv_handle* h) { return h ? h->map_n : 0; }
+
+int pv_timemap_channels(const pv_handle* h) { return (h && h->map_n > 0) ? h->map_channels : 0; }
 
 pv_status pv_timemap_process(pv_handle* h, const float* x, long long ldx, long long n_samples, int channels,
                              int frames, pv_float2* spec, long long ld_spec, float* out, long long ldo,

@@ -156,6 +156,14 @@ struct pv_handle {
     // carries, [max_channels][max_runs][bins_pad] each (allocated by the first set, zeroed)
     int map_n = 0, map_imax = 0;
     pvhost::DevBuf<pv::MapEntry> d_map;
+    // pv_timemap_set_channels: a map per channel (map_channels > 0; 0: the shared map or none).
+    // d_map then holds max_channels rows of max_frames entries (grown by the first such set),
+    // d_map_counts the channels' frame counts (passed to the kernels only when one is below
+    // map_n: map_counted); map_imax_c the highest row index of each channel's counted frames.
+    int map_channels = 0, map_counted = 0;
+    long long map_rows = 0;  // rows of max_frames entries d_map holds (1: the shared map only)
+    pvhost::DevBuf<int> d_map_counts;
+    std::vector<int> map_imax_c;
     pvhost::DevBuf<unsigned> d_map_sum, d_map_carry;
     // pv_pitchmap_set: the variable-rate resampler of pv_pitchmap_process (blocks of hop samples)
     // and the final frames n of the pitch map (0: no pitch map; the time map is then the
@@ -232,9 +240,17 @@ struct pv_varresampler {
     int nblocks = 0;        // 0: no map
     int copy = 0;           // every step 2^32, no fraction: the rows shifted by copy_shift samples
     long long copy_shift = 0;
-    int span4_max = 0;      // the largest staged span of the map's tiles
+    int span4_max = 0;      // the largest staged span of the map's tiles (over the channels)
     pvhost::DevBuf<pv::VarBlock> d_blocks;  // [max_blocks], zeroed
     pvhost::DevBuf<pv::VarTile> d_tiles;    // [ceil(max_blocks block / kVarTile)], zeroed
+    // pv_varresampler_set_maps: records per channel (map_channels > 0; 0: the shared map or none),
+    // [cap_channels][max_blocks] and [cap_channels][tiles as above], and per channel the shift of
+    // a channel that is a copy (every step 2^32, no fraction in its start), -1 for a filtered one;
+    // copy != 0 then says that every channel is a copy
+    int map_channels = 0, cap_channels = 0;
+    pvhost::DevBuf<pv::VarBlock> d_blocks_c;
+    pvhost::DevBuf<pv::VarTile> d_tiles_c;
+    pvhost::DevBuf<long long> d_shift_c;
     pvhost::DevBuf<float2> d_win;           // [kVarWinN + 1]
 };
 
@@ -360,6 +376,9 @@ hipError_t resample_rows(const pv_resampler* rs, const float* x, long long ldx, 
 // pv_pitchmap_process runs the second into the scratch rows): the handle's kind, the refusals of a
 // call with channels > 0, and the launches (the caller holds the device guard and the profile call)
 pv_status timemap_set(const char* fn, pv_handle* h, const double* pos, int n_out);
+// pv_timemap_set_channels (pv_pitchmap_set_channels installs its stretch maps through it)
+pv_status timemap_set_channels(const char* fn, pv_handle* h, const double* pos, long long ld_pos, const int* counts,
+                               int channels, int n_out);
 pv_status timemap_handle_check(const char* fn, const pv_handle* h);
 pv_status timemap_check(const char* fn, const pv_handle* h, const float* x, int channels, int frames,
                         const float* out, long long ldo);

@@ -135,24 +135,31 @@ inline void set_reset_args(SynParams* p, const ResetArgs& a) {
 }
 
 // The time-map stretch (pv_timemap.hip).  Output frame u is built at analysis
-// position i_u + a_u: map[u] = {i_u, a_u} (pv_timemap_split), one map for all channels.
+// position i_u + a_u: map[u] = {i_u, a_u} (pv_timemap_split): one map for all channels, or one row
+// of `ld_map` entries per channel (pv_timemap_set_channels).
 struct MapEntry {
     int idx;
     float frac;
 };
 // The map modes' view of SynParams (no pitch map, no envelope; `frames`, F, nruns count output
 // frames; `carry` is k_map_carry's, Phi at every run's first frame): the map and the number of
-// analysed rows, every idx <= aframes - 1 (checked by the host)
+// analysed rows, every idx <= aframes - 1 (checked by the host).  Channel c reads map + c * ld_map
+// (0: the shared map) and has counts[c] output frames (nullptr: `frames`); the frames from
+// counts[c] on contribute nothing.
 struct MapArgs {
     const MapEntry* map;
     int aframes;
+    long long ld_map;
+    const int* counts;
 };
 __host__ __device__ inline MapArgs map_args(const SynParams& p) {
-    return MapArgs{reinterpret_cast<const MapEntry*>(p.src_first), p.env_stride};
+    return MapArgs{reinterpret_cast<const MapEntry*>(p.src_first), p.env_stride, p.ld_env, p.src_cnt};
 }
 inline void set_map_args(SynParams* p, const MapArgs& a) {
     p->src_first = reinterpret_cast<const int*>(a.map);
     p->env_stride = a.aframes;
+    p->ld_env = a.ld_map;
+    p->src_cnt = a.counts;
 }
 // k_map_sum: sum[(c * nruns + r) * bins_pad + k] = the sum over run r's output frames u of
 // Delta(i_u)[k] = P(i_u + 1)[k] - P(i_u)[k] (0 for i_u = aframes - 1), modulo 2^32;
@@ -165,6 +172,8 @@ struct MapScanParams {
     int L, bins_pad;
     int packed;                        // PV_SPEC_PACKED rows
     const MapEntry* map;
+    long long ld_map;                  // entries between the channels' maps (0: one shared map)
+    const int* counts;                 // output frames per channel (nullptr: `frames`)
     unsigned* sum;
     unsigned* carry;
 };

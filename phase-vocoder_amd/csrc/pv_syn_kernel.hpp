@@ -30,7 +30,8 @@ namespace pv {
 //         frames, each from the two analysis rows around its map position (map_args,
 //         pv_kernels.h); the running phase Phi, a 32-bit fraction of a turn, takes the place of
 //         the unwrap count in the wave's registers (its carry is k_map_carry's).  Launched with
-//         q = 1 (QPOW2): there is no output-phase denominator.
+//         q = 1 (QPOW2): there is no output-phase denominator.  With a map per channel the
+//         channel's own row of the map and its own frame count (frames past it are zero).
 // Overlap-add: a position is final once the frame that starts after it has been added;
 // final samples are stored straight to `out`.
 //   DT > 0 (out hop = 128 DT, L <= 1024): in registers.  After the inverse FFT's last pass
@@ -112,7 +113,12 @@ __global__ __launch_bounds__(256, (L <= 256) ? 4 : (L == 512) ? (MODE >= kModeLo
     const int c = blockIdx.y;
     const int run = blockIdx.x * 4 + w;
     const int t0 = run * p.F;
-    const int nfr = max(0, min(p.F, p.frames - t0));  // real frames of this wave's run
+    int frames_c = p.frames;
+    if constexpr (mode_is_map(MODE)) {  // a map per channel may end before `frames` (map_args, pv_kernels.h)
+        const int* counts = map_args(p).counts;
+        if (counts) frames_c = __builtin_amdgcn_readfirstlane(counts[c]);
+    }
+    const int nfr = max(0, min(p.F, frames_c - t0));  // real frames of this wave's run
     float* outc = p.out + (long long)c * p.ldo;
     const long long obase = (long long)t0 * hs;
 
@@ -153,7 +159,7 @@ __global__ __launch_bounds__(256, (L <= 256) ? 4 : (L == 512) ? (MODE >= kModeLo
         const MapArgs ma = map_args(p);
         syn_run<L, MODE, DT, QPOW2, LANEK, NR, NoResetRun, MapRun>(
             p, SynCarve{twl, twsl, tiles, rings, gainl, ekl, jkl, srcl}, tw0, lane, w, c, t0, nfr, M, phprev, acc,
-            NoResetRun{}, MapRun{ma.map + t0, ma.aframes});
+            NoResetRun{}, MapRun{ma.map + (long long)c * ma.ld_map + t0, ma.aframes});
     } else
     syn_run<L, MODE, DT, QPOW2, LANEK, NR>(
         p, SynCarve{twl, twsl, tiles, rings, gainl, ekl, jkl, srcl}, tw0, lane, w, c, t0, nfr, M, phprev, acc);

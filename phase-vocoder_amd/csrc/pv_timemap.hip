@@ -9,6 +9,9 @@
 // does not depend on the run length.  Nothing waits on another workgroup, nothing allocates or
 // synchronises: all capturable.  Every row index (i_u, i_u + 1 <= aframes - 1) and every run
 // and carry row is in range by the host's checks (pv_timemap_set, pv_timemap_process).
+// Channel c reads the map at map + c * ld_map (0: one map for all channels) and has counts[c]
+// output frames (nullptr: `frames`; pv_timemap_set_channels): a run past a
+// channel's count sums nothing and synthesises zeros.
 #include "pv_syn_kernel.hpp"
 
 namespace pv {
@@ -27,7 +30,9 @@ __global__ __launch_bounds__(256) void k_map_sum(MapScanParams p) {
     const int run = blockIdx.x * 4 + w;
     if (run >= p.nruns) return;
     const int t0 = run * p.F;
-    const int nfr = min(p.F, p.frames - t0);
+    const int frames_c = p.counts ? __builtin_amdgcn_readfirstlane(p.counts[c]) : p.frames;
+    const int nfr = max(0, min(p.F, frames_c - t0));
+    const MapEntry* mapc = p.map + (long long)c * p.ld_map + t0;
     const float2* specc = p.spec + (long long)c * p.ld_spec;
     const bool packed = p.packed != 0;
     auto load = [&](int t, unsigned (&P)[E + 1]) {
@@ -45,7 +50,7 @@ __global__ __launch_bounds__(256) void k_map_sum(MapScanParams p) {
     for (int i = 0; i <= E; ++i) S[i] = P1[i] = 0u;
     int held = -1;  // the row P1 holds (wave-uniform)
     for (int u = 0; u < nfr; ++u) {
-        const int iu = __builtin_amdgcn_readfirstlane(p.map[t0 + u].idx);
+        const int iu = __builtin_amdgcn_readfirstlane(mapc[u].idx);
         if (iu >= alast) continue;
         if (held == iu) {
 #pragma unroll
@@ -71,7 +76,7 @@ __global__ __launch_bounds__(64) void k_map_carry(MapScanParams p) {
     const int BP = p.bins_pad;
     // PV_SPEC_PACKED rows: bins 0 and L are the sign bits of slot 0 {s0, sL}
     const bool real_bin = p.packed && (k == 0 || k == p.L);
-    const int i0 = p.map[0].idx;
+    const int i0 = p.map[(long long)c * p.ld_map].idx;
     const float2 v = p.spec[(long long)c * p.ld_spec + (long long)i0 * p.spec_stride + (real_bin ? 0 : k)];
     const float phi = !real_bin ? v.y : (__float_as_uint(k == 0 ? v.x : v.y) >> 31) ? kPi : 0.0f;
     unsigned M = phase_turns(phi);

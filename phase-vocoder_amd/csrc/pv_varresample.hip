@@ -19,6 +19,9 @@
 //                       j >= 1, f and 1 - f each rounded once from fq (no cancellation);
 //                     - the Kaiser window by linear interpolation in a table over |u| in [0, 1].
 //   k_var_copy      every step 2^32, no fraction: the shifted rows as they are.
+// With maps per channel (pv_varresampler_set_maps) a workgroup reads its channel's
+// records, and a channel that is a copy beside filtered ones copies its tiles in k_var_resample
+// (a test that is uniform over the workgroup): k_var_copy's values, bit for bit.
 //
 // No state, no allocation, no synchronisation: capturable.  A kernel file of its own, so every
 // other kernel keeps its code.
@@ -65,8 +68,19 @@ __global__ __launch_bounds__(256) void k_var_resample(VarResampleParams p) {
     __shared__ float2 wt[kVarWinLen];
     const int tid = threadIdx.x;
     const int tile = blockIdx.x % p.ntiles, ch = blockIdx.x / p.ntiles;
-    const VarTile tr = p.tiles[tile];
     const float* row = p.x + (long long)ch * p.ldx;
+    if (p.copy_shift) {
+        const long long shift = p.copy_shift[ch];  // (uniform over the workgroup, before any barrier)
+        if (shift >= 0) {
+            float* dst = p.y + (long long)ch * p.ldy;
+            for (int k = 0; k < kVarTile / 256; ++k) {
+                const long long m = (long long)tile * kVarTile + tid + 256 * k;
+                if (m < p.n_out) dst[m] = (shift + m < p.n_in) ? row[shift + m] : 0.0f;
+            }
+            return;
+        }
+    }
+    const VarTile tr = p.tiles[(long long)ch * p.ld_tiles + tile];
     // the staged span starts at the tile's first input sample, moved down by `mis` < 4 samples to
     // a 16-byte boundary of global memory (whatever the row's own alignment)
     const int mis = (int)(((long long)(reinterpret_cast<uintptr_t>(row) >> 2) + tr.base) & 3);
@@ -89,12 +103,13 @@ __global__ __launch_bounds__(256) void k_var_resample(VarResampleParams p) {
 
     const float* xs = reinterpret_cast<const float*>(xs4);
     float* yrow = p.y + (long long)ch * p.ldy;
+    const VarBlock* blocks = p.blocks + (long long)ch * p.ld_blocks;
     for (int k = 0; k < kVarTile / 256; ++k) {
         const long long m = (long long)tile * kVarTile + tid + 256 * k;
         if (m >= p.n_out) break;
         const unsigned b = (unsigned)m / (unsigned)p.B;
         const unsigned j = (unsigned)m - b * (unsigned)p.B;
-        const VarBlock blk = p.blocks[b];
+        const VarBlock blk = blocks[b];
         const long long t = blk.T + (long long)j * blk.d;
         const long long i = t >> 32;
         const unsigned fq = (unsigned)t;
@@ -144,8 +159,10 @@ hipError_t launch_var_resample(int channels, const VarResampleParams& p, int spa
 }
 
 __global__ __launch_bounds__(256) void k_var_copy(const float* x, long long ldx, long long n_in, long long shift,
-                                                  float* y, long long ldy, long long n_out, int ntiles) {
+                                                  const long long* shifts, float* y, long long ldy, long long n_out,
+                                                  int ntiles) {
     const int tile = blockIdx.x % ntiles, ch = blockIdx.x / ntiles;
+    if (shifts) shift = shifts[ch];
     const float* src = x + (long long)ch * ldx;
     float* dst = y + (long long)ch * ldy;
     const long long m0 = (long long)tile * 1024 + threadIdx.x;
@@ -156,12 +173,12 @@ __global__ __launch_bounds__(256) void k_var_copy(const float* x, long long ldx,
     }
 }
 
-hipError_t launch_var_copy(const float* x, long long ldx, long long n_in, long long shift, float* y, long long ldy,
-                           long long n_out, int channels, hipStream_t s) {
+hipError_t launch_var_copy(const float* x, long long ldx, long long n_in, long long shift, const long long* shifts,
+                           float* y, long long ldy, long long n_out, int channels, hipStream_t s) {
     const long long ntiles = (n_out + 1023) / 1024;
     if (ntiles * channels > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_var_copy, dim3((unsigned)(ntiles * channels)), dim3(256), 0, s, x, ldx, n_in, shift, y, ldy,
-                       n_out, (int)ntiles);
+    hipLaunchKernelGGL(k_var_copy, dim3((unsigned)(ntiles * channels)), dim3(256), 0, s, x, ldx, n_in, shift, shifts, y,
+                       ldy, n_out, (int)ntiles);
     return hipGetLastError();
 }
 

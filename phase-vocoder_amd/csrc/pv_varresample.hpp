@@ -43,16 +43,23 @@ struct VarResampleParams {
     long long ldy, n_out;
     const VarBlock* blocks;
     const VarTile* tiles;
+    // maps per channel (pv_varresampler_set_maps): channel c reads blocks +
+    // c * ld_blocks and tiles + c * ld_tiles (0: one map for all channels).  copy_shift (nullptr
+    // for the shared map): per channel the shift of a channel that is a copy, y[m] = x[shift + m],
+    // or -1 for a filtered one
+    long long ld_blocks, ld_tiles;
+    const long long* copy_shift;
     const float2* win;
     int B;
     int ntiles;       // tiles per channel: grid.x = ntiles * channels
     float win_scale;  // kVarWinN / Z * 2^-32: (float)Sq * win_scale * |tau| indexes the window table
 };
 
-// span4_max: the largest span4 of the map's tiles (the launch's dynamic LDS)
+// span4_max: the largest span4 of the map's tiles, over the channels (the launch's dynamic LDS)
 hipError_t launch_var_resample(int channels, const VarResampleParams& p, int span4_max, hipStream_t s);
-// every step 2^32 and no fraction: y[m] = x[shift + m], 0 past n_in
-hipError_t launch_var_copy(const float* x, long long ldx, long long n_in, long long shift, float* y, long long ldy,
-                           long long n_out, int channels, hipStream_t s);
+// every step 2^32 and no fraction: y[m] = x[shift + m], 0 past n_in; shifts: one per channel
+// (nullptr: `shift` for all)
+hipError_t launch_var_copy(const float* x, long long ldx, long long n_in, long long shift, const long long* shifts,
+                           float* y, long long ldy, long long n_out, int channels, hipStream_t s);
 
 }  // namespace pv

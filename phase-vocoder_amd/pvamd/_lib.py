@@ -236,6 +236,10 @@ def lib():
     L.pv_timemap_set.restype = i
     L.pv_timemap_frames.argtypes = [vp]
     L.pv_timemap_frames.restype = i
+    L.pv_timemap_set_channels.argtypes = [vp, vp, ll, vp, i, i]
+    L.pv_timemap_set_channels.restype = i
+    L.pv_timemap_channels.argtypes = [vp]
+    L.pv_timemap_channels.restype = i
     L.pv_timemap_process.argtypes = [vp, vp, ll, ll, i, i, vp, ll, vp, ll, vp]
     L.pv_timemap_process.restype = i
     L.pv_varresampler_create.argtypes = [i, i, i, i, ctypes.POINTER(vp)]
@@ -246,6 +250,10 @@ def lib():
     L.pv_varresample_steps.restype = i
     L.pv_varresampler_set_map.argtypes = [vp, ll, vp, i]
     L.pv_varresampler_set_map.restype = i
+    L.pv_varresampler_set_maps.argtypes = [vp, i, vp, vp, ll, i]
+    L.pv_varresampler_set_maps.restype = i
+    L.pv_varresample_map_channels.argtypes = [vp]
+    L.pv_varresample_map_channels.restype = i
     L.pv_varresample_length.argtypes = [vp]
     L.pv_varresample_length.restype = ll
     L.pv_varresample.argtypes = [vp, vp, ll, ll, i, vp, ll, ll, vp]
@@ -254,6 +262,8 @@ def lib():
     L.pv_pitchmap_plan.restype = i
     L.pv_pitchmap_set.argtypes = [vp, vp, vp, i, i]
     L.pv_pitchmap_set.restype = i
+    L.pv_pitchmap_set_channels.argtypes = [vp, vp, ll, vp, ll, i, i, i]
+    L.pv_pitchmap_set_channels.restype = i
     L.pv_pitchmap_output_length.argtypes = [vp]
     L.pv_pitchmap_output_length.restype = ll
     L.pv_pitchmap_process.argtypes = [vp, vp, ll, ll, i, i, vp, ll, vp, ll, vp]

@@ -59,11 +59,27 @@ class VarResampler:
     def set_map(self, steps_or_ratios, start: int = 0):
         """pv_varresampler_set_map: one entry per block; an integer array holds steps (2^32 = ratio
         1), a floating one ratios (converted by `ratio_steps`).  start: the first output's input
-        position in units of 2^-32 samples.  A setup call (not capturable)."""
+        position in units of 2^-32 samples.  A setup call (not capturable).
+        A 2-D [channels, blocks] array is a map per channel (pv_varresampler_set_maps): row c
+        and start[c] (a scalar start: the same for every channel) for channel c of a call."""
         a = np.asarray(steps_or_ratios)
+        if a.ndim == 2:
+            C, nb = a.shape
+            step = (ratio_steps(a).reshape(C, nb) if a.dtype.kind == "f"
+                    else np.ascontiguousarray(a, dtype=np.int64))
+            st = np.ascontiguousarray(np.broadcast_to(np.asarray(start, dtype=np.int64), (C,)))
+            _lib.check(self._L.pv_varresampler_set_maps(self._h, int(C), st.ctypes.data_as(_vp),
+                                                        step.ctypes.data_as(_vp), int(nb), int(nb)),
+                       "pv_varresampler_set_maps")
+            return
         step = ratio_steps(a) if a.dtype.kind == "f" else np.ascontiguousarray(a, dtype=np.int64).reshape(-1)
         _lib.check(self._L.pv_varresampler_set_map(self._h, int(start), step.ctypes.data_as(_vp), int(step.size)),
                    "pv_varresampler_set_map")
+
+    @property
+    def map_channels(self) -> int:
+        """pv_varresample_map_channels: the channels of maps per channel; 0 without a map or with the shared one"""
+        return int(self._L.pv_varresample_map_channels(self._h))
 
     @property
     def length(self) -> int:

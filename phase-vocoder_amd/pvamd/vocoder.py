@@ -63,6 +63,8 @@ def pitch_correction(track, a4: float, scale=CHROMATIC, strength_min: float = 0.
     """pv_pitch_correct_plan (pure host, no GPU): the {f0, strength} track of one voice
     ([frames, 2], numpy or a tensor, `PhaseVocoder.pitch_track`'s row) -> the pitch ratios
     (float64) that snap it to the scale, one per output frame, for `PhaseVocoder.set_pitch_map`.
+    A [channels, frames, 2] track (`pitch_track`'s whole result) gives [channels, n] ratios, one
+    plan per row, for `set_pitch_map`'s 2-D form; pos is then one row for all voices or one per voice.
     a4: the frequency of A4 in cycles per sample (440 / sample rate); scale: a 12-bit mask (bit i
     = pitch class i is allowed, 0 = C; `MAJOR`, `CHROMATIC`) or an iterable of pitch classes;
     frames with a strength below strength_min hold the last correction; retune in (0, 1]: 1 snaps
@@ -71,8 +73,17 @@ def pitch_correction(track, a4: float, scale=CHROMATIC, strength_min: float = 0.
     if hasattr(track, "detach"):
         track = track.detach().cpu().numpy()
     tr = np.ascontiguousarray(track, dtype=np.float32)
+    if tr.ndim == 3 and tr.shape[2] == 2:
+        if pos is not None:
+            pos = np.asarray(pos, dtype=np.float64)
+            if pos.ndim == 2 and pos.shape[0] != tr.shape[0]:
+                raise ValueError("pos must be one row for all voices or one per voice")
+        rows = [pitch_correction(tr[c], a4, scale, strength_min, retune,
+                                 None if pos is None else (pos[c] if pos.ndim == 2 else pos))
+                for c in range(tr.shape[0])]
+        return np.stack(rows) if rows else np.empty((0, 0), dtype=np.float64)
     if tr.ndim != 2 or tr.shape[1] != 2:
-        raise ValueError("track must be [frames, 2]: one voice's {f0, strength}")
+        raise ValueError("track must be [frames, 2]: one voice's {f0, strength}, or [channels, frames, 2]")
     if isinstance(scale, (int, np.integer)):
         mask = int(scale)
     else:
@@ -432,14 +443,31 @@ class PhaseVocoder:
         return out, spec
 
     # -------------------------------------------------------------- time-map stretch
-    def set_time_map(self, positions):
+    def set_time_map(self, positions, counts=None):
         """pv_timemap_set: output frame u of `time_map_process` is built at the fractional
         analysis position positions[u] (frames, float64; finite, >= 0; need not be monotonic:
         a freeze, a scrub and a reverse are maps; see `rate_map`).  One map for all channels;
-        at most max_frames entries.  STANDARD time-stretch handles at scale 1.  None clears it."""
+        at most max_frames entries.  STANDARD time-stretch handles at scale 1.  None clears it.
+        A 2-D [channels, n_out] array is a map per channel (pv_timemap_set_channels): channel c
+        of `time_map_process` uses row c, of which counts[c] entries count (None: all n_out); its
+        output past output_length(counts[c]) is zero."""
         if positions is None:
             self._call(self._L.pv_timemap_set(self._h, None, 0), "pv_timemap_set")
             return
+        if np.ndim(positions) == 2:
+            pos = np.ascontiguousarray(positions, dtype=np.float64)
+            vp = ctypes.c_void_p
+            cnt = None
+            if counts is not None:
+                cnt = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
+                if cnt.size != pos.shape[0]:
+                    raise ValueError("counts must have one entry per channel")
+            self._call(self._L.pv_timemap_set_channels(self._h, pos.ctypes.data_as(vp), int(pos.shape[1]),
+                                                       None if cnt is None else cnt.ctypes.data_as(vp),
+                                                       int(pos.shape[0]), int(pos.shape[1])), "pv_timemap_set_channels")
+            return
+        if counts is not None:
+            raise ValueError("counts go with a [channels, n_out] map")
         pos = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1)
         self._call(self._L.pv_timemap_set(self._h, pos.ctypes.data_as(ctypes.c_void_p), int(pos.size)),
                    "pv_timemap_set")
@@ -447,6 +475,11 @@ class PhaseVocoder:
     @property
     def time_map_frames(self) -> int:
         return int(self._L.pv_timemap_frames(self._h))
+
+    @property
+    def time_map_channels(self) -> int:
+        """pv_timemap_channels: the channels of a map per channel; 0 without a map or with the shared one"""
+        return int(self._L.pv_timemap_channels(self._h))
 
     def time_map_process(self, x, frames: int | None = None, n_samples: int | None = None, spec=None,
                          out=None, stream=None, spectrum: bool = True):
@@ -476,9 +509,21 @@ class PhaseVocoder:
         ratios[u] (1/4 .. 4): a glide, a vibrato, a correction curve, tempo and pitch varying
         independently.  It installs the time map of the stretch (`time_map_frames` then reads its
         length) and the handle's variable-rate resampler (quality 0 fast, 1 best).  One map for
-        all channels; a setup call.  positions=None clears it; so does a later `set_time_map`."""
+        all channels; a setup call.  positions=None clears it; so does a later `set_time_map`.
+        2-D [channels, n] positions and ratios are a pitch map per channel
+        (pv_pitchmap_set_channels): one plan per row, n final frames for every channel."""
         if positions is None:
             self._call(self._L.pv_pitchmap_set(self._h, None, None, 0, 0), "pv_pitchmap_set")
+            return
+        if np.ndim(positions) == 2 or np.ndim(ratios) == 2:
+            pos = np.ascontiguousarray(positions, dtype=np.float64)
+            rat = np.ascontiguousarray(ratios, dtype=np.float64)
+            if pos.ndim != 2 or pos.shape != rat.shape:
+                raise ValueError("positions and ratios must both be [channels, n]")
+            vp = ctypes.c_void_p
+            self._call(self._L.pv_pitchmap_set_channels(self._h, pos.ctypes.data_as(vp), int(pos.shape[1]),
+                                                        rat.ctypes.data_as(vp), int(rat.shape[1]), int(pos.shape[0]),
+                                                        int(pos.shape[1]), int(quality)), "pv_pitchmap_set_channels")
             return
         pos = np.ascontiguousarray(positions, dtype=np.float64).reshape(-1)
         rat = np.ascontiguousarray(ratios, dtype=np.float64).reshape(-1)
