@@ -90,7 +90,9 @@ extern "C" {
                                 pv_resident_min_channels, pv_pitch_track / pv_pitch_correct_plan,
                                 pv_timemap_set_channels / pv_timemap_channels,
                                 pv_varresampler_set_maps / pv_varresample_map_channels,
-                                pv_pitchmap_set_channels) */
+                                pv_pitchmap_set_channels, pv_rt_pitchmap_reserve /
+                                pv_rt_pitchmap_latency / pv_rt_pitchmap_push /
+                                pv_rt_pitchmap_host_ratios) */
 
 typedef struct pv_handle pv_handle;
 
@@ -644,8 +646,9 @@ pv_status pv_varresample(pv_varresampler* vr, const float* x, long long ldx, lon
  *     longest's length are exact zeros, which is what the resampler reads past a row's end), and
  *     a channel at ratio 1 throughout is pv_timemap_process of its positions.  The clear, the
  *     output length and the refusals are pv_pitchmap_set's.
- * One map for all channels unless set per channel.  pv_rt, the harmoniser, the stream segments and
- * the envelope warp have no pitch map.  pv_process and every other entry point are unchanged by
+ * One map for all channels unless set per channel.  pv_rt has a streaming form with a ratio per
+ * pushed frame (pv_rt_pitchmap_push); the harmoniser, the stream segments and the envelope warp
+ * have no pitch map.  pv_process and every other entry point are unchanged by
  * one. */
 pv_status pv_pitchmap_plan(int n_samps, int hop, const double* pos, const double* ratio, int n, double* pos_s,
                            int cap_s, int* n_s, long long* step, int cap_steps, int* n_steps);
@@ -701,7 +704,9 @@ pv_status pv_pitchmap_process(pv_handle* h, const float* x, long long ldx, long 
  *   finite.
  * One correction curve per call: one voice, or channels that share a voice; a batch of voices is
  * one call per channel's track and one pv_pitchmap_set_channels (pv_pitchmap_set is one map for
- * all channels unless set per channel).  pv_rt and pv_main have no tracker. */
+ * all channels unless set per channel).  pv_rt and pv_main have no tracker: a live correction
+ * tracks the rows pv_rt_pitchmap_push returns with pv_pitch_track on a batch handle of the same
+ * geometry and feeds the next callback's ratios. */
 #define PV_PITCH_TRACK_DEFAULT_KAPPA 0.9f
 typedef struct pv_pitch_correct {
     int abi_version;      /* = PV_ABI_VERSION */
@@ -735,7 +740,8 @@ pv_status pv_rt_push(pv_rt* rt, const float* in, long long ldi, int nframes, flo
 /* Capture one callback of `nframes` frames into a hipGraph: pinned host input -> device,
  * pv_rt_push, device -> pinned host output.  The pinned buffers are planar
  * [channels][nframes*hop] and [channels][nframes*out_hop] (pv_rt_host_buffers); after
- * pv_rt_pitch_reserve (below) the callback is pv_rt_pitch_push and the output buffer
+ * pv_rt_pitch_reserve or pv_rt_pitchmap_reserve (below) the callback is pv_rt_pitch_push or
+ * pv_rt_pitchmap_push, whichever reserve succeeded later, and the output buffer
  * [channels][nframes*hop]. */
 pv_status pv_rt_capture(pv_rt* rt, int nframes);
 pv_status pv_rt_host_buffers(pv_rt* rt, float** host_in, float** host_out);
@@ -789,6 +795,64 @@ pv_status pv_rt_pitch_reserve(pv_rt* rt, int quality, int max_nframes);
 int pv_rt_pitch_latency(const pv_rt* rt);
 pv_status pv_rt_pitch_push(pv_rt* rt, const float* in, long long ldi, int nframes, float* out,
                            long long ldo, pv_float2* spec, long long ld_spec, void* stream);
+
+/* Real-time pitch map: pv_pitchmap_process as a stream.  Every pushed frame
+ * carries one fp32 pitch ratio per channel, read from device memory when the launch runs, so a
+ * captured callback is steered by writing its ratio buffer.  It honours pv_rt_set_phase_lock.
+ * The pv_rt must be STANDARD + PV_TIME_SHIFT with out_hop == hop.  Per channel:
+ *   rows     row t >= 0 is analysis frame t of the stream prefixed with N - hop zeros (pv_rt_push's
+ *            analysis, bit for bit); P(t) its phases as 32-bit fractions of a turn (pv_timemap_*).
+ *   steps    pushed frame t carries r_t; r' = min(max(r_t, ratio_min), ratio_max), a NaN reading as
+ *            ratio_min; d = (int64)(r' 2^32), exact.  Frame 0's ratio is read and ignored; for
+ *            t >= 1, d_{t-1} = d.  Span b runs from row b to row b+1 with the step d_b, and is built
+ *            by the callback that analyses row b+1.  Sigma_0 = 0, Sigma_{b+1} = Sigma_b + hop d_b
+ *            (64-bit, units of 2^-32 samples).
+ *   stretch  stretched frame v, at t_v = v hop 2^32, lies in the span b with Sigma_b <= t_v <
+ *            Sigma_{b+1} (0 to 4 per span): pv_timemap_process's frame at position b + a,
+ *            a = (float)((double)(t_v - Sigma_b) / (double)(hop d_b)): magnitude fmaf(a, mag(b+1) -
+ *            mag(b), mag(b)); Phi(0) = P(0), Phi += P(b+1) - P(b) modulo 2^32 after every stretched
+ *            frame of span b; Psi = Phi, or locked P(b)[k] + (Phi - P(b))[own(k)] with the peaks
+ *            and owners of the interpolated magnitudes.  Gain and overlap-add at `hop` are the
+ *            handle's.  S is the resulting stream, S[n] = 0 for n < 0.
+ *   output   block b, hop samples: sample j reads S at T = Sigma_b + j d_b through
+ *            pv_varresample's filter of a block with step d_b (Sq_b, W_b, h_b as there; computed on
+ *            the device in fp64 by the same operations).  No copy shortcut at ratio 1.
+ *   latency  with d_min, d_max the steps of ratio_min, ratio_max and W_max = W(d_max):
+ *            G = ceil(W_max 2^32 / (hop d_min)).  Pushed frame t emits block t - 1 - G (zeros below
+ *            block 0): emitted sample m' is y[m' - (G+1) hop], and pv_rt_pitchmap_latency is
+ *            (G+1) hop.  G callbacks are what it takes for every stretched sample a block reads to
+ *            be final.  [0.84, 1.19], fast preset, hop >= 64: G = 1; [1/4, 4]: G = 5 at hop 64.
+ * A push of nframes frames consumes nframes*hop samples and emits exactly nframes*hop.  The stream
+ * does not depend on how it is cut into pushes (bit for bit); no state grows with its length (the
+ * positions are relative to the scratch row, the counters saturate).  Tolerance bound like
+ * pv_pitchmap_process, no bit-exact contract for the samples.
+ * pv_rt_pitchmap_reserve (a setup call: allocates, not capturable) sizes and zeroes the state for
+ *   pushes of up to max_nframes frames; calling it again replaces preset, range and capacity and
+ *   zeroes the pitch map's own state (not the input history and the overlap accumulator it
+ *   shares with pv_rt_push: pv_rt_reset starts a new stream).  PV_ERR_UNSUPPORTED: a PV_PITCH_SHIFT handle, out_hop != hop,
+ *   hop < 16.  PV_ERR_ARG: a captured callback exists, bad quality, max_nframes <= 0, a range
+ *   outside [1/4, 4], with ratio_min > ratio_max or with a NaN, G > 64, (G + max_nframes) hop >=
+ *   2^28.  PV_ERR_NOMEM: nothing changes (the feature stays off if it was).  The later successful
+ *   call of this or pv_rt_pitch_reserve decides what pv_rt_capture records.
+ * pv_rt_pitchmap_latency: 0 for NULL or before a successful reserve.
+ * pv_rt_pitchmap_push: device pointers; in, out, spec as pv_rt_push's with out[c*ldo + i],
+ *   i < nframes*hop; ratio[c*ldr + f], f < nframes, or NULL for 1 throughout.  Two launches
+ *   (profile names rt_map, rt_varresample), no allocation, no synchronisation: capturable.
+ *   PV_ERR_ARG before a successful reserve, with nframes > max_nframes, or ldr < nframes with more
+ *   than one channel.
+ * pv_rt_pitchmap_host_ratios: after pv_rt_capture recorded pv_rt_pitchmap_push, the pinned
+ *   [channels][nframes] buffer the captured callback reads its ratios from (device-mapped like the
+ *   input buffer; a copy node where the runtime cannot map it), filled with 1 by the capture.
+ *   PV_ERR_ARG without such a capture.
+ * pv_rt_reset zeroes the pitch map's state too.  Switching between pv_rt_push, pv_rt_pitch_push
+ * and pv_rt_pitchmap_push in mid-stream without a reset gives a finite, in-bounds but unspecified
+ * stream.  Every refusal sets a pv_last_error text. */
+pv_status pv_rt_pitchmap_reserve(pv_rt* rt, int quality, int max_nframes, float ratio_min, float ratio_max);
+int pv_rt_pitchmap_latency(const pv_rt* rt);
+pv_status pv_rt_pitchmap_push(pv_rt* rt, const float* in, long long ldi, int nframes, const float* ratio,
+                              long long ldr, float* out, long long ldo, pv_float2* spec, long long ld_spec,
+                              void* stream);
+pv_status pv_rt_pitchmap_host_ratios(pv_rt* rt, float** host_ratio);
 
 /* ---------------------------------------------------------------- harmoniser
  * K voices, voice k = PITCH_SHIFT by ratios[k] of the same input, all from ONE analysis

@@ -33,13 +33,13 @@ pv_status fail(pv_status s, const std::string& msg);
 
 // kernel ids of the per-launch profile and their names (pv_profile_read), index for index
 enum { KA, KRS, KC, KS, KSEAM, KCA, KRT, KF, KSL, KENV, KSF, KRES, KRTR, KSW, KON, KPK, KRST, KSR, KMS, KMC, KSM,
-       KVR, KRD, KPT, kNumKernels };
+       KVR, KRD, KPT, KRTM, KRTV, kNumKernels };
 inline constexpr const char* kKernelNames[] = {"analysis", "runsum", "carry", "synthesis", "seam",
                                                "compat_analysis", "rt", "fused", "synthesis_locked",
                                                "envelope", "synthesis_formant", "resample", "rt_resample",
                                                "synthesis_warp", "onset", "pick", "reset", "synthesis_reset",
                                                "map_sum", "map_carry", "synthesis_map", "var_resample",
-                                               "resident", "pitch"};
+                                               "resident", "pitch", "rt_map", "rt_varresample"};
 static_assert(sizeof(kKernelNames) / sizeof(kKernelNames[0]) == kNumKernels, "one name per kernel id");
 
 // Move-only owner of one hipMalloc (Pinned: hipHostMalloc, device-mapped) allocation.  Converts
@@ -212,10 +212,27 @@ struct pv_rt {
     int pitch_on = 0, pitch_P = 1, pitch_Q = 1, pitch_W = 0, pitch_H = 0, pitch_D = 0, pitch_max = 0;
     pvhost::DevBuf<float> d_prow, d_ptab;
     long long ld_prow = 0;
-    // captured callback
+    // pv_rt_pitchmap_reserve: the real-time pitch map's preset, ratio range and
+    // plan, and its stream state per channel: d_mprev [bins_pad] the last analysed row {mag, bits
+    // of P}, d_mphi [bins_pad] Phi, d_mstate, d_mring [ring_cap] the steps not yet emitted, d_mrow
+    // [row_len] the scratch row [K history | final stretched samples]; d_mwin: the window table
+    int pmap_on = 0, pmap_quality = 0, pmap_max = 0;
+    float pmap_rmin = 1.0f, pmap_rmax = 1.0f;
+    pvtab::RtPitchmapPlan pmap_plan{};
+    pvhost::DevBuf<float2> d_mprev, d_mwin;
+    pvhost::DevBuf<unsigned> d_mphi;
+    pvhost::DevBuf<pv::RtMapState> d_mstate;
+    pvhost::DevBuf<long long> d_mring;
+    pvhost::DevBuf<float> d_mrow;
+    // what pv_rt_capture records: the later successful reserve decides
+    enum { kPush = 0, kPitchPush = 1, kPitchmapPush = 2 };
+    int callback = kPush;
+    // captured callback (h_ratio / d_ratio / m_ratio: the ratios of a captured pv_rt_pitchmap_push,
+    // [channels][g_nframes])
     int g_nframes = 0;
-    pvhost::DevBuf<float, true> h_in, h_out;
-    pvhost::DevBuf<float> d_in, d_out;
+    pvhost::DevBuf<float, true> h_in, h_out, h_ratio;
+    pvhost::DevBuf<float> d_in, d_out, d_ratio;
+    float* m_ratio = nullptr;
     hipStream_t g_stream = nullptr;
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;

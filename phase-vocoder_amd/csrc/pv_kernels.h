@@ -351,6 +351,57 @@ struct RtResampleParams {
     unsigned off;                      // W Q - D P >= 0; (n_out - 1) P + off < 2^31
 };
 
+// real-time pitch map (pv_rt_pitchmap.hip): two launches per callback.  Per
+// channel the stream keeps RtMapState (all zero at a stream's start; every position is relative to
+// the scratch row, every counter saturates: nothing grows with the stream), a ring of the steps
+// d_b whose blocks are not yet emitted, oldest first, and the scratch row
+//   row[0 .. K)           the K >= W_max final stretched samples below row[K]'s position
+//   row[K .. K + fill)    the final stretched samples from there on
+// (S[n] = 0 for n < 0 is the zeroed row of a stream's start).
+struct RtMapState {
+    long long off;   // the next stretched frame's offset inside the current span, 2^-32 samples
+    long long rpos;  // start of the next output block relative to row[K], 2^-32 samples (< 2^32
+                     // between callbacks)
+    int rows;        // 0: the next analysed row is the stream's first; 1 otherwise
+    int fill;        // see above
+    int nsteps;      // steps waiting in the ring
+    int emitted;     // output blocks emitted, saturating at G + 1 (the first G + 1 are zeros)
+};
+// k_rt_map: k_rt's analysis (rt: its block; out, ldo, hs, phprev, M, tcount and the unwrap and
+// pitch tables are not used), then per pushed frame the stretched frames of the span that frame
+// closes, appended to the row; the frame's step goes into the ring.
+struct RtMapParams {
+    RtParams rt;
+    const float* ratio;                // [C][nframes] (row stride ldr), or nullptr: 1
+    long long ldr;
+    float ratio_min, ratio_max;
+    float2* prev;                      // [C][bins_pad] {mag, bits of P} of the last analysed row
+    unsigned* phi;                     // [C][bins_pad] Phi, fractions of a turn
+    RtMapState* st;                    // [C]
+    long long* ring;                   // [C][ring_cap]
+    int ring_cap;                      // >= G + the largest nframes
+    float* row;                        // [C][ld_row]
+    long long ld_row;
+    int K;
+};
+// k_rt_varresample: nframes output blocks of hop samples per channel from the row, then the row's
+// unread tail moves to its front.  The host has sized the row and the ring
+// (pvtab::rt_pitchmap_plan): neither kernel checks anything.
+struct RtVarParams {
+    float* row;
+    long long ld_row;
+    int K;
+    float* out;                        // [C][nframes * hop] (row stride ldo)
+    long long ldo;
+    RtMapState* st;
+    long long* ring;
+    int ring_cap;
+    const float2* win;                 // the window table of pv_varresample.hpp
+    float win_scale;
+    int channels, nframes, hop, G;
+    double rolloff, Z;                 // the preset's (Sq_b and W_b are computed here, in fp64)
+};
+
 // harmoniser mix: dst[c][i] = sum_k gain[k] * src[k][c][i]
 struct MixParams {
     const float* src;
@@ -421,6 +472,10 @@ constexpr int kRtModeLocked = 6;  // (= kModeLocked, pv_lock.hpp)
 hipError_t launch_rt(int L, int mode, const RtParams& p, hipStream_t s);
 size_t rt_lds_bytes(int L);
 hipError_t launch_rt_resample(const RtResampleParams& p, hipStream_t s);
+// real-time pitch map (pv_rt_pitchmap.hip): the geometries k_rt_map is built for, and the launches
+bool rt_map_kernel(int L);
+hipError_t launch_rt_map(int L, int lock, const RtMapParams& p, hipStream_t s);
+hipError_t launch_rt_varresample(const RtVarParams& p, hipStream_t s);
 hipError_t launch_window_gain(const float* win, float* dwin, float* gain, int n, hipStream_t s);
 hipError_t launch_overlap_test(const float* in, const float* win, const float* back, float* out,
                                int n, int hop, hipStream_t s);

@@ -423,6 +423,7 @@ void var_block_filter(long long d, int quality, unsigned* Sq, int* W) {
 }
 
 double resample_zero_crossings(int quality) { return kResamplePresets[quality][0]; }
+double resample_rolloff(int quality) { return kResamplePresets[quality][1]; }
 
 // the Kaiser window over u = i / n with the sinc's 1 / pi: {w(u_i) / pi, the rise to the next
 // entry} for i < n (each value rounded to fp32 first: the interpolation ends on the next entry),
@@ -439,6 +440,29 @@ void var_window_table(int quality, int n, int len, std::vector<float>& tab) {
         tab[2 * i] = w[i];
         tab[2 * i + 1] = w[i + 1] - w[i];
     }
+}
+
+// The real-time pitch map's latency and buffer sizes (integers; the steps are exact: an fp32 at or
+// above 1/4 is a multiple of 2^-26)
+bool rt_pitchmap_plan(int hop, int quality, float ratio_min, float ratio_max, int max_nframes, RtPitchmapPlan* out) {
+    if (hop < 1 || max_nframes < 1 || (quality != 0 && quality != 1)) return false;
+    if (!(ratio_min >= 0.25f) || !(ratio_max <= 4.0f) || !(ratio_min <= ratio_max)) return false;
+    RtPitchmapPlan p{};
+    p.d_min = (long long)(ratio_min * 0x1p32f);
+    p.d_max = (long long)(ratio_max * 0x1p32f);
+    unsigned sq;
+    var_block_filter(p.d_max, quality, &sq, &p.W_max);
+    const long long den = (long long)hop * p.d_min;
+    p.G = (int)((((long long)p.W_max << 32) + den - 1) / den);
+    p.latency = (p.G + 1) * hop;
+    p.K = (p.W_max + 3) & ~3;
+    // ((G + max_nframes) hop < 2^28 and d_max <= 2^34: the product stays below 2^62)
+    if ((long long)(p.G + (long long)max_nframes) * hop >= (1LL << 28)) return false;
+    const long long span = ((long long)(p.G + max_nframes) * hop * p.d_max + kVarOne - 1) >> 32;
+    p.row_len = (p.K + span + hop + 4 + 3) & ~3LL;
+    p.ring_cap = (long long)p.G + max_nframes;
+    *out = p;
+    return true;
 }
 
 // The pitch map's plan (pv_pitchmap_plan): the time map of the stretch and the steps of the

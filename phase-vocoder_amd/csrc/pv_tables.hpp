@@ -118,11 +118,27 @@ bool varresample_steps(const double* ratio, int n, long long* step);
 // a block's cutoff Sq (even, s = Sq / 2^32) and half width W for its step d
 void var_block_filter(long long d, int quality, unsigned* Sq, int* W);
 double resample_zero_crossings(int quality);  // Z of the preset
+double resample_rolloff(int quality);         // its rolloff
 // the kernel's window table: n intervals over |u| in [0, 1], `len` > n entries {value / pi, rise}
 void var_window_table(int quality, int n, int len, std::vector<float>& tab);
 // pos, ratio [n] -> pos_s [n_s], step [ceil((n hop + N - hop) / hop)]; false on a bad argument
 bool pitchmap_plan(int N, int hop, const double* pos, const double* ratio, int n, std::vector<double>& pos_s,
                    std::vector<long long>& step);
+
+// ---- real-time pitch map (pv_rt_pitchmap_reserve): what follows from the hop,
+// the preset, the ratio range and the largest push.  d_min, d_max: the steps (int64)(r 2^32) of the
+// range's ends; W_max = W(d_max); G = ceil(W_max 2^32 / (hop d_min)), the callbacks an output block
+// waits; latency = (G + 1) hop; K >= W_max (a multiple of 4): the row's history samples; row_len:
+// floats of a channel's scratch row, K + ceil((G + max_nframes) hop d_max / 2^32) + hop + 4 rounded
+// up to a multiple of 4 (the final samples a push can leave behind the history);
+// ring_cap = G + max_nframes steps.  false: hop or max_nframes < 1, a quality other than 0, 1, a
+// range with a NaN, outside [1/4, 4] or with ratio_min > ratio_max, (G + max_nframes) hop >= 2^28.
+struct RtPitchmapPlan {
+    long long d_min, d_max;
+    int W_max, G, latency, K;
+    long long row_len, ring_cap;
+};
+bool rt_pitchmap_plan(int hop, int quality, float ratio_min, float ratio_max, int max_nframes, RtPitchmapPlan* out);
 
 // ---- pitch correction (pv_pitch_correct_plan): track [frames] {f0, strength}
 // -> ratio [n], one per output frame (pos: its analysis position, nullptr: u); false on a bad

@@ -33,35 +33,7 @@ namespace pv {
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 
-namespace {
-
-constexpr float kPiF = 0x1.921fb6p+1f;
-constexpr float kTwoPiF = 0x1.921fb6p+2f;
-
-// sin(a), |a| <= pi/2: the odd Taylor polynomial of degree 11 (its next term is 5.7e-8 at pi/2)
-__device__ __forceinline__ float sin_folded(float a) {
-    const float a2 = a * a;
-    float c = -0x1.ae6456p-26f;         // -1 / 11!
-    c = fmaf(c, a2, 0x1.71de3ap-19f);   //  1 / 9!
-    c = fmaf(c, a2, -0x1.a01a02p-13f);  // -1 / 7!
-    c = fmaf(c, a2, 0x1.111112p-7f);    //  1 / 5!
-    c = fmaf(c, a2, -0x1.555556p-3f);   // -1 / 3!
-    return fmaf(a2 * a, c, a);
-}
-// sin(2 pi p / 2^32).  sin(pi - a) = sin(a): a phase in the second or third quarter turn is
-// folded about the quarter turn in integers; the angle then lies in [-pi/2, pi/2].
-__device__ __forceinline__ float sin_turn(unsigned p) {
-    const unsigned q = (p + 0x40000000u) >= 0x80000000u ? 0x80000000u - p : p;
-    return sin_folded((float)(int)q * (kTwoPiF * 0x1p-32f));
-}
-// the same of p / 2^64, for the two taps next to the centre: |tau| may be tiny there, and the
-// angle keeps its relative precision only if the conversion to fp32 sees all 64 bits
-__device__ __forceinline__ float sin_turn64(unsigned long long p) {
-    const unsigned long long q = (p + (1ull << 62)) >= (1ull << 63) ? (1ull << 63) - p : p;
-    return sin_folded((float)(long long)q * (kTwoPiF * 0x1p-64f));
-}
-
-}  // namespace
+using namespace vartap;  // sin_turn, sin_turn64, kPiF (pv_varresample.hpp)
 
 __global__ __launch_bounds__(256) void k_var_resample(VarResampleParams p) {
     extern __shared__ __attribute__((aligned(16))) f4 xs4[];

@@ -21,6 +21,10 @@
 //   tables_dump resident mode pitch L_ana L_syn hop hs q_pow2 q k_lane F tail_len
 //       prints "supported threshold": resident_supported of the geometry and, with PV_RESIDENT
 //       from the environment, resident_min_channels
+//   tables_dump rtpitchmap hop quality ratio_min ratio_max max_nframes
+//       prints "d_min d_max W_max G latency K row_len ring_cap": the real-time pitch map's plan
+//       (pv_rt_pitchmap_reserve; the ratios as strtof reads them, hexadecimal floats included), or
+//       "refused"
 // [file] absent or "-": stdout.
 #include <cstdint>
 #include <cstdio>
@@ -67,7 +71,8 @@ int usage() {
                  "       tables_dump warp N hop out_hop [file]\n"
                  "       tables_dump choose C T N hop_div mode effect scale wgs_per_cu waves_per_wg\n"
                  "       tables_dump balance frames F\n"
-                 "       tables_dump resident mode pitch L_ana L_syn hop hs q_pow2 q k_lane F tail_len\n");
+                 "       tables_dump resident mode pitch L_ana L_syn hop hs q_pow2 q k_lane F tail_len\n"
+                 "       tables_dump rtpitchmap hop quality ratio_min ratio_max max_nframes\n");
     return 2;
 }
 
@@ -208,6 +213,20 @@ int resident(int argc, char** argv) {
     return 0;
 }
 
+// rtpitchmap hop quality ratio_min ratio_max max_nframes -> the plan, or "refused"
+int rtpitchmap(int argc, char** argv) {
+    if (argc < 7) return usage();
+    RtPitchmapPlan p{};
+    if (!rt_pitchmap_plan(std::atoi(argv[2]), std::atoi(argv[3]), std::strtof(argv[4], nullptr),
+                          std::strtof(argv[5], nullptr), std::atoi(argv[6]), &p)) {
+        std::printf("refused\n");
+        return 0;
+    }
+    std::printf("%lld %lld %d %d %d %d %lld %lld\n", p.d_min, p.d_max, p.W_max, p.G, p.latency, p.K, p.row_len,
+                p.ring_cap);
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -218,5 +237,6 @@ int main(int argc, char** argv) {
     if (cmd == "choose") return choose(argc, argv);
     if (cmd == "balance") return balance(argc, argv);
     if (cmd == "resident") return resident(argc, argv);
+    if (cmd == "rtpitchmap") return rtpitchmap(argc, argv);
     return dump_tables(argc, argv);
 }

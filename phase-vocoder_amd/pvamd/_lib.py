@@ -188,6 +188,14 @@ def lib():
     L.pv_rt_pitch_latency.restype = i
     L.pv_rt_pitch_push.argtypes = [vp, vp, ll, i, vp, ll, vp, ll, vp]
     L.pv_rt_pitch_push.restype = i
+    L.pv_rt_pitchmap_reserve.argtypes = [vp, i, i, f, f]
+    L.pv_rt_pitchmap_reserve.restype = i
+    L.pv_rt_pitchmap_latency.argtypes = [vp]
+    L.pv_rt_pitchmap_latency.restype = i
+    L.pv_rt_pitchmap_push.argtypes = [vp, vp, ll, i, vp, ll, vp, ll, vp, ll, vp]
+    L.pv_rt_pitchmap_push.restype = i
+    L.pv_rt_pitchmap_host_ratios.argtypes = [vp, fpp]
+    L.pv_rt_pitchmap_host_ratios.restype = i
     L.pv_fft_c2c.argtypes = [vp, vp, i, i, i, vp]
     L.pv_fft_c2c.restype = i
     L.pv_harmonizer_create.argtypes = [ctypes.POINTER(pv_config), ctypes.POINTER(ctypes.c_float), i,

@@ -11,6 +11,11 @@ A time-stretch vocoder can also shift the pitch live: `set_phase_lock` turns ide
 locking on, `reserve_pitch` adds the streaming resampler, and `pitch_push` (or the captured
 callback) then takes nframes*hopSize samples and gives nframes*hopSize shifted ones,
 `pitch_latency` output samples late.
+
+A vocoder at scale 1 can follow a pitch ratio that changes from frame to frame:
+`reserve_pitch_map` sets the preset and the ratio range, `pitch_map_push` (or the captured
+callback, `callback(x, ratios)`) takes one ratio per channel and frame beside the samples, and
+the stream comes out `pitch_map_latency` samples late.
 """
 from __future__ import annotations
 
@@ -40,6 +45,7 @@ class RealTimeVocoder:
         self.spec_stride = (self.spec_bins + 7) & ~7
         self._graph_frames = 0
         self._pitch = False
+        self.host_ratios = None
         if phase_lock:
             self.set_phase_lock(True)
 
@@ -113,6 +119,43 @@ class RealTimeVocoder:
                                             _ptr(spec), lds, self._stream(stream)), "pv_rt_pitch_push")
         return out
 
+    # ---------------------------------------------------------- pitch map
+    def reserve_pitch_map(self, quality: int = 0, max_frames: int = 1, *, ratio_min: float = 0.5,
+                          ratio_max: float = 2.0):
+        """pv_rt_pitchmap_reserve: the state of `pitch_map_push` for pushes of up to max_frames
+        frames and pitch ratios in [ratio_min, ratio_max] (inside [1/4, 4]; a ratio outside the
+        range is clamped to it).  The range sets the latency.  Scale-1 time-stretch vocoders only,
+        before `capture`."""
+        _lib.check(self._L.pv_rt_pitchmap_reserve(self._h, int(quality), int(max_frames), float(ratio_min),
+                                                  float(ratio_max)), "pv_rt_pitchmap_reserve")
+        self._pitch = True
+
+    @property
+    def pitch_map_latency(self) -> int:
+        """output samples by which `pitch_map_push`'s stream is delayed (0 before `reserve_pitch_map`)"""
+        return int(self._L.pv_rt_pitchmap_latency(self._h))
+
+    def pitch_map_push(self, x, ratios=None, out=None, spec=None, stream=None):
+        """x: [C, nframes*hop] CUDA float32, ratios: [C, nframes] CUDA float32 (None: 1) -> out
+        [C, nframes*hop]: the stream shifted in pitch by each frame's ratio (device, async)."""
+        torch = _torch()
+        x = x.unsqueeze(0) if x.dim() == 1 else x
+        C, n = x.shape
+        assert C == self.channels and n % self.hopSize == 0 and x.stride(-1) == 1
+        nf = n // self.hopSize
+        ldr = 0
+        if ratios is not None:
+            ratios = ratios.unsqueeze(0) if ratios.dim() == 1 else ratios
+            assert ratios.shape == (C, nf) and ratios.dtype == torch.float32 and ratios.stride(-1) == 1
+            ldr = ratios.stride(0)
+        if out is None:
+            out = torch.empty((C, n), dtype=torch.float32, device=x.device)
+        lds = 0 if spec is None else spec.stride(0) // 2
+        _lib.check(self._L.pv_rt_pitchmap_push(self._h, _ptr(x), x.stride(0), nf, _ptr(ratios), ldr, _ptr(out),
+                                               out.stride(0), _ptr(spec), lds, self._stream(stream)),
+                   "pv_rt_pitchmap_push")
+        return out
+
     # ---------------------------------------------------------- captured callback
     def capture(self, nframes: int = 1):
         _lib.check(self._L.pv_rt_capture(self._h, int(nframes)), "pv_rt_capture")
@@ -126,11 +169,21 @@ class RealTimeVocoder:
         # zero-copy numpy views of the pinned callback buffers
         self.host_in = np.ctypeslib.as_array(fi, shape=(self.channels, ni))
         self.host_out = np.ctypeslib.as_array(fo, shape=(self.channels, no))
+        # after reserve_pitch_map: the pinned ratios the callback reads, [C, nframes], all 1
+        self.host_ratios = None
+        fr = ctypes.POINTER(ctypes.c_float)()
+        if self._L.pv_rt_pitchmap_host_ratios(self._h, ctypes.byref(fr)) == _lib.PV_OK:
+            self.host_ratios = np.ctypeslib.as_array(fr, shape=(self.channels, nframes))
 
-    def callback(self, x: np.ndarray | None = None) -> np.ndarray:
+    def callback(self, x: np.ndarray | None = None, ratios: np.ndarray | None = None) -> np.ndarray:
         """One synchronous callback: x (host [C, nframes*hop], or None when host_in was
         filled in place) -> host_out view [C, nframes*outHop] ([C, nframes*hop] after
-        `reserve_pitch`)."""
+        `reserve_pitch` or `reserve_pitch_map`).  ratios (host [C, nframes], after
+        `reserve_pitch_map`): written into host_ratios, which keeps them for the callbacks after."""
+        if ratios is not None:
+            if self.host_ratios is None:
+                raise _lib.PVError(_lib.PV_ERR_ARG, "callback(ratios=...): the captured callback is not pitch_map_push")
+            self.host_ratios[...] = np.asarray(ratios, dtype=np.float32).reshape(self.host_ratios.shape)
         src = None
         if x is not None:
             x = np.ascontiguousarray(x, dtype=np.float32)
