@@ -21,9 +21,18 @@
 // forever.  Roles are wave-uniform (the wave's index), which with the dispatcher's placement
 // gives every SIMD one wave of each role.
 //
-// Results are the split path's bit for bit (tests/test_gpu_resident.py):
-//   rows      the pieces k_std_analysis is made of (load_frame, win_mul; res_ana_frame:
-//             fft_run, bin_l_real, polar_pair — pv_frame.hpp, pv_resident.hpp);
+// An analysis wave's frames are N / 2 samples apart, so in its steady state (frames wholly inside
+// the input) it loads only the new half of each frame and rotates the register roles instead of
+// moving the old half (ResRot, pv_resident.hpp); the channel's last frames load whole,
+// bounds-checked, in a loop of their own.  This translation unit is built without SLP
+// vectorisation (-fno-slp-vectorize, Makefile), as pv_analysis.hip is: the per-bin scalar chains
+// of the split and the atan2 stay scalar (profiles/resident_ana_c3.txt).
+//
+// Results are the split path's bit for bit (tests/test_gpu_resident.py,
+// tests/test_gpu_resident_tail.py):
+//   rows      the pieces k_std_analysis is made of (frame_load_vec / frame_load_checked, win_mul;
+//             res_ana_frame: fft_run, bin_l_real, the mirrored-pair split with atan2_pv2 and
+//             half_sqrt — pv_frame.hpp, pv_resident.hpp);
 //   decisions the contract's one-rounding formula against the previous frame's phase for every
 //             frame, phi(-1) = 0 — what k_synthesis does inside a run and k_carry at a run's
 //             first frame; the revolution accumulator R = ((p M) mod q) / q is exact, so carrying
@@ -79,26 +88,59 @@ __global__ __launch_bounds__(64 * kResWaves, 3) void k_resident(ResidentParams p
         // frames whose N samples are all inside [0, n) take vector loads (x is aligned: the
         // host's predicate), the last N / hop of a channel the bounds-checked path
         const long long lastfull = (p.n >= N) ? (p.n - N) / p.hop : -1;
-        auto load = [&](int t, float2 (&xr)[E]) { load_frame<E>(xc, t, p.hop, p.n, lastfull, lane, xr); };
+        // the wave's frames are t = role + 2 i, i < nmine, one per step; its first nfast are fast
+        const int nmine = (frames > role) ? (frames - role + 1) / 2 : 0;
+        const long long tl = min(lastfull, (long long)frames - 1);
+        const int nfast = (tl >= role) ? (int)((tl - role) / 2) + 1 : 0;
         float2 wv[E];  // the window samples 2 (lane + 64 q) + {0, 1}, for the whole channel
         {
             const float2* w2 = reinterpret_cast<const float2*>(p.win) + lane;
 #pragma unroll
             for (int q = 0; q < E; ++q) wv[q] = w2[64 * q];
         }
+        using Rot = ResRot<E>;  // the input advances N / 2 samples per frame of a wave (hop = N / 4)
         float2 xr[E];
-        if (role < frames) load(role, xr);
-        for (int j = 0; j < nsteps; ++j) {
-            const int t = 2 * j + role;
-            if (t < frames) {
-                float2 z[E];
+        // Steady state: a frame of rotation phase r windows its pairs out of the rotated
+        // registers, puts the next frame's new pairs (in flight during this frame) into the
+        // registers that frees, and transforms.  The prefetch index is clamped: the last fast
+        // frame reloads its own pairs, which nothing reads (the frames after it load whole).
+        auto fast_frame = [&](auto rc, int i) {
+            constexpr int r = decltype(rc)::value, rn = (r + 1) % Rot::RR;
+            float2 z[E];
 #pragma unroll
-                for (int q = 0; q < E; ++q) win_mul(xr[q], wv[q], z[q]);
-                if (t + 2 < frames) load(t + 2, xr);  // in flight during this frame
-                res_ana_frame<L>(z, tile, twl, twsl, tw0, lane, ring + (t & (kResRing - 1)) * RG::ROW);
+            for (int q = 0; q < E; ++q) win_mul(xr[Rot::reg(q, r)], wv[q], z[q]);
+            float2 nw[E];
+            frame_load_vec<E, E - Rot::D>(xc, (long long)(role + 2 * min(i + 1, nfast - 1)) * p.hop, lane, nw);
+#pragma unroll
+            for (int q = E - Rot::D; q < E; ++q) xr[Rot::reg(q, rn)] = nw[q];
+            res_ana_frame<L>(z, tile, twl, twsl, tw0, lane, ring + ((role + 2 * i) & (kResRing - 1)) * RG::ROW);
+            res_barrier();
+        };
+        int i = 0;
+        if (nfast > 0) {
+            frame_load_vec<E>(xc, (long long)role * p.hop, lane, xr);
+            // one loop of RR frames with an exit after each: it is left at either phase, and
+            // holds vector loads only
+            for (;;) {
+                fast_frame(IC<0>{}, i);
+                if (++i == nfast) break;
+                fast_frame(IC<1>{}, i);
+                if (++i == nfast) break;
             }
+        }
+        // the channel's last frames (at most N / hop of them, two per wave): whole frames, every
+        // sample checked against n — whatever phase the loop above was left at
+        for (; i < nmine; ++i) {
+            const int t = role + 2 * i;
+            frame_load_checked<E>(xc, (long long)t * p.hop, p.n, lane, xr);
+            float2 z[E];
+#pragma unroll
+            for (int q = 0; q < E; ++q) win_mul(xr[q], wv[q], z[q]);
+            res_ana_frame<L>(z, tile, twl, twsl, tw0, lane, ring + (t & (kResRing - 1)) * RG::ROW);
             res_barrier();
         }
+        // the steps without a frame of this wave (the drain): every wave executes nsteps barriers
+        for (; i < nsteps; ++i) res_barrier();
         return;
     }
     // -------------------------------------------------------------------- synthesis wave
@@ -213,7 +255,8 @@ static_assert(ResGeo<512>::BYTES <= 40 * 1024, "four workgroups per CU");
 bool resident_kernel(int L, int hs) { return L == 512 && hs == 128; }
 
 hipError_t launch_resident(int L, int channels, const ResidentParams& p, hipStream_t s) {
-    if (!resident_kernel(L, p.hs)) return hipErrorInvalidValue;
+    // (hop = N / 4: the analysis waves' register rotation, ResRot)
+    if (!resident_kernel(L, p.hs) || p.hop != L / 2) return hipErrorInvalidValue;
     hipLaunchKernelGGL((k_resident<512, 1>), dim3(channels), dim3(64 * kResWaves), ResGeo<512>::BYTES, s, p);
     return hipGetLastError();
 }

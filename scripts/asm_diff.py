@@ -2,7 +2,7 @@
 """Device assembly of a git revision against the working tree's, per kernel file (developer tool).
 
 Compiles every kernel translation unit of phase-vocoder_amd/csrc to gfx950 assembly (device
-only, the flags of scripts/isa_static.py, -fno-slp-vectorize for pv_analysis) twice — from the
+only, the flags of scripts/isa_static.py, -fno-slp-vectorize for pv_analysis and pv_resident) twice — from the
 sources of REV, taken with `git show REV:path` into a temporary directory, and from the working
 tree — and counts the lines that differ.  Before the comparison the `.file` and `.ident` lines
 are dropped, the per-compilation `__hip_cuid_<hash>` symbol is normalised, and every --rename
@@ -26,7 +26,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from isa_static import FLAGS  # noqa: E402
 
 CSRC = "phase-vocoder_amd/csrc"
-EXTRA = {"pv_analysis": ["-fno-slp-vectorize"]}
+EXTRA = {"pv_analysis": ["-fno-slp-vectorize"], "pv_resident": ["-fno-slp-vectorize"]}
 
 
 def checkout(rev, dst):

@@ -31,8 +31,9 @@ KERNELS = {
     ("c3", "analysis"): ("pv_analysis.hip", ["-fno-slp-vectorize"], "_ZN2pv14k_std_analysisILi512ELb0ELi2ELb1E", 9),
     ("c3", "synthesis"): ("pv_kernels.hip", [], "_ZN2pv11k_synthesisILi512ELi0ELi1ELb1ELb1E", 17),
     # the channel-resident launch (PV_RESIDENT): one kernel, two per-frame loops — the analysis
-    # waves' (no global store: its rows go to LDS) and the synthesis wave's (resident_loops)
-    ("c3", "resident"): ("pv_resident.hip", [], "_ZN2pv10k_residentILi512ELi1E", (9, 17)),
+    # waves' (no global store: its rows go to LDS) and the synthesis wave's (resident_loops);
+    # the Makefile's per-object flag
+    ("c3", "resident"): ("pv_resident.hip", ["-fno-slp-vectorize"], "_ZN2pv10k_residentILi512ELi1E", (9, 17)),
     # config 4 (bench.py: no spectrum handed back, pitch 1.5): the instantiation analysing
     # lane registers 0 .. 11 (bins < 768; 12 square roots, no bin L)
     ("c4", "analysis"): ("pv_analysis.hip", ["-fno-slp-vectorize"], "_ZN2pv14k_std_analysisILi1024ELb0ELi4ELb1ELi12E", 12),
@@ -150,24 +151,38 @@ def frame_loop(asm, prefix, trans_pf, extra):
 
 def resident_loops(asm, prefix, trans_pf, extra):
     """k_resident's two frame loops: the synthesis wave's is frame_loop's (sines, cosines and
-    the output stores); the analysis waves' is the innermost loop with the frame's square roots
-    and no sine.  The analysis loop carries the bounds-checked input loads of the channel's last
-    frames beside the vector loads, so its count is an upper bound of the steady state."""
+    the output stores); the analysis waves' is the steady-state loop of two frames per trip (one
+    per rotation phase of the shifted input, vector loads only, left by a forward branch after
+    either frame), not the bounds-checked loop of the channel's last frames.  Candidates are the
+    backward branches that span whole frames (a multiple of the frame's square roots, one barrier
+    per frame, no sine); the cheapest per frame is taken, widened to the largest candidate around
+    it that costs the same per frame within 1 % (a branch back to a block laid out inside the
+    loop spans one phase only)."""
     ana_pf, syn_pf = trans_pf
     syn = frame_loop(asm, prefix, syn_pf, extra)
 
     def count(seg, ops):
         return sum(1 for o, _ in seg if o.startswith(ops))
-    cands = [(a, b, seg) for a, b, seg in loops_of(asm, prefix)
-             if count(seg, ("v_sqrt",)) >= ana_pf and count(seg, ("v_sin", "v_cos")) == 0]
-    inner = [c for c in cands if not any(o is not c and c[0] <= o[0] and o[1] <= c[1] for o in cands)]
-    if syn is None or not inner:
+
+    def frames_of(seg):
+        return count(seg, ("v_sqrt",)) // ana_pf
+
+    def per_frame(c):
+        return price(c[2], extra)[1] / frames_of(c[2])
+    cands = [c for c in loops_of(asm, prefix)
+             if frames_of(c[2]) >= 1 and count(c[2], ("v_sqrt",)) % ana_pf == 0
+             and count(c[2], ("s_barrier",)) == frames_of(c[2]) and count(c[2], ("v_sin", "v_cos")) == 0]
+    if syn is None or not cands:
         return None
-    ana = min(inner, key=lambda c: c[1] - c[0])[2]
+    best = min(cands, key=per_frame)
+    around = [c for c in cands if c[0] <= best[0] and best[1] <= c[1] and per_frame(c) <= 1.01 * per_frame(best)]
+    ana = max(around, key=lambda c: c[1] - c[0])[2]
     a_cnt, a_cyc = price(ana, extra)
+    a_fpl = frames_of(ana)
+    a_cyc /= a_fpl
     s_seg, s_fpl, s_cyc, s_cnt = syn
     return {"symbol": prefix,
-            "analysis_loop": {"loop_instructions": len(ana), "frames_per_trip": 1, "counts_per_trip": dict(a_cnt),
+            "analysis_loop": {"loop_instructions": len(ana), "frames_per_trip": a_fpl, "counts_per_trip": dict(a_cnt),
                               "valu_cycles_per_frame": round(a_cyc, 1)},
             "synthesis_loop": {"loop_instructions": len(s_seg), "frames_per_trip": s_fpl,
                                "counts_per_trip": dict(s_cnt), "valu_cycles_per_frame": round(s_cyc / s_fpl, 1)},
