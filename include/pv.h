@@ -854,6 +854,53 @@ pv_status pv_rt_pitchmap_push(pv_rt* rt, const float* in, long long ldi, int nfr
                               void* stream);
 pv_status pv_rt_pitchmap_host_ratios(pv_rt* rt, float** host_ratio);
 
+/* Real-time harmoniser: V voices of the real-time pitch map per channel from one
+ * analysis of each pushed frame, mixed with a gain per voice and frame.  Two launches per callback
+ * whatever V is.  It honours pv_rt_set_phase_lock.  Per channel c and voice v:
+ *   voice    y_v is pv_rt_pitchmap_push's stream of the channel's input with the voice's ratios:
+ *            the same rows, clamp (a NaN ratio reads as ratio_min), steps, spans, stretched frames,
+ *            block filter and tap order, frame 0's ratio ignored, the same latency (G+1) hop with G
+ *            from the ratio range: common to all voices.  No voice depends on another.
+ *   gain     the gain pushed with frame t >= 1 belongs to output block b = t - 1, the block the
+ *            ratio pushed with frame t steers, and waits with the step through the latency.  Frame
+ *            0's gain is ignored; a NaN gain reads as 0; nothing else is clamped.  Sample j of block
+ *            b has g(j) = fmaf((float)(j+1) * (1.0f / (float)hop), g_b - g_prev, g_prev) with
+ *            g_prev = g_{b-1}, g_{-1} = g_0: a linear ramp over the block (a voice that turns on or
+ *            off does not click), exactly g_b when the gain does not change.
+ *   mix      mix[j] = fmaf(g_{V-1}(j), y_{V-1}[j], ... fmaf(g_0(j), y_0[j], +0)), the voices in
+ *            rising order, fp32.  Blocks below block 0 are zeros.
+ * There is no dry path of its own: a voice at ratio 1 is the input behind the same latency (the
+ * identity map), which is how a caller adds the dry signal aligned with the wet one.
+ * pv_rt_harmonizer_max_voices: pure host; 8, 8, 8, 4 for n_samps 256, 512, 1024, 2048, else 0.
+ * pv_rt_harmonizer_reserve (a setup call: allocates, not capturable): pv_rt_pitchmap_reserve's
+ *   preconditions and refusals, and PV_ERR_ARG for voices outside [1, max_voices(n_samps)].
+ *   Calling it again replaces voices, preset, range and capacity and zeroes the harmoniser's state.
+ *   PV_ERR_NOMEM: nothing changes (the feature stays off if it was).  The later successful call of
+ *   this, pv_rt_pitchmap_reserve or pv_rt_pitch_reserve decides what pv_rt_capture records.
+ * pv_rt_harmonizer_voices, pv_rt_harmonizer_latency: 0 for NULL or before a successful reserve.
+ * pv_rt_harmonizer_push: device pointers; in, spec as pv_rt_pitchmap_push's; ratio and gain
+ *   [channels][voices][nframes], element (c*V + v)*ld_ctl + f (ratio NULL: 1 throughout, gain NULL:
+ *   1 / V); mix[c*ldo + i], i < nframes*hop; voices_out (nullable) [voices][channels][nframes*hop],
+ *   element (v*channels + c)*ld_voice + i: every voice's own stream.  Two launches (profile names
+ *   rt_hmap, rt_hresample), no allocation, no synchronisation: capturable.  PV_ERR_ARG before a
+ *   successful reserve, with nframes > max_nframes, or with ld_ctl < nframes.
+ * pv_rt_harmonizer_host_controls: after pv_rt_capture recorded pv_rt_harmonizer_push (its callback
+ *   emits the mix), the pinned [channels][voices][nframes] buffers the captured callback reads its
+ *   ratios and gains from, filled with 1 and 1 / V by the capture (either argument may be NULL).
+ *   PV_ERR_ARG without such a capture.
+ * pv_rt_reset zeroes the harmoniser's state too; it shares the input history with the other pushes,
+ * so switching between them in mid-stream without a reset gives a finite, in-bounds but unspecified
+ * stream.  Every refusal sets a pv_last_error text. */
+int pv_rt_harmonizer_max_voices(int n_samps);
+pv_status pv_rt_harmonizer_reserve(pv_rt* rt, int voices, int quality, int max_nframes, float ratio_min,
+                                   float ratio_max);
+int pv_rt_harmonizer_voices(const pv_rt* rt);
+int pv_rt_harmonizer_latency(const pv_rt* rt);
+pv_status pv_rt_harmonizer_push(pv_rt* rt, const float* in, long long ldi, int nframes, const float* ratio,
+                                const float* gain, long long ld_ctl, float* mix, long long ldo, float* voices_out,
+                                long long ld_voice, pv_float2* spec, long long ld_spec, void* stream);
+pv_status pv_rt_harmonizer_host_controls(pv_rt* rt, float** host_ratio, float** host_gain);
+
 /* ---------------------------------------------------------------- harmoniser
  * K voices, voice k = PITCH_SHIFT by ratios[k] of the same input, all from ONE analysis
  * and one unwrap scan (cfg: STANDARD; effect and scale are ignored).  voices_out[k*ld_voice

@@ -2,7 +2,8 @@
 // per-channel stream state + an optional captured graph of one callback (pinned host in ->
 // device -> pv_rt_push -> pinned host out); the real-time pitch shift adds the locked stretch
 // and the streaming resampler, the real-time pitch map a pitch ratio per pushed
-// frame (pv_rt_pitchmap_*).
+// frame (pv_rt_pitchmap_*); the real-time harmoniser (pv_api_rt_harmon.cpp;
+// DESIGN.md §3.17) shares the captured callback.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -14,38 +15,7 @@
 
 using namespace pvhost;
 
-namespace {
-// the captured callback; the stream stays for the next capture
-void rt_release_graph(pv_rt* rt) {
-    if (rt->exec) (void)hipGraphExecDestroy(rt->exec);
-    if (rt->graph) (void)hipGraphDestroy(rt->graph);
-    rt->exec = nullptr;
-    rt->graph = nullptr;
-    rt->h_in.reset();
-    rt->h_out.reset();
-    rt->d_in.reset();
-    rt->d_out.reset();
-    rt->h_ratio.reset();
-    rt->d_ratio.reset();
-    rt->m_ratio = nullptr;
-    rt->g_nframes = 0;
-}
-// samples per frame a callback emits: hop once pv_rt_pitch_reserve or pv_rt_pitchmap_reserve has
-// succeeded, else out hop
-int rt_out_hop(const pv_rt* rt) { return rt->callback != pv_rt::kPush ? rt->h->hop : rt->h->hs; }
-// what a callback runs: the push of the later successful reserve, else pv_rt_push (ratio: the
-// pitch map's [channels][nframes] ratios)
-pv_status rt_callback_push(pv_rt* rt, const float* in, long long ldi, int nframes, const float* ratio, float* out,
-                           long long ldo, hipStream_t s) {
-    switch (rt->callback) {
-        case pv_rt::kPitchmapPush:
-            return pv_rt_pitchmap_push(rt, in, ldi, nframes, ratio, nframes, out, ldo, nullptr, 0, s);
-        case pv_rt::kPitchPush: return pv_rt_pitch_push(rt, in, ldi, nframes, out, ldo, nullptr, 0, s);
-        default: return pv_rt_push(rt, in, ldi, nframes, out, ldo, nullptr, 0, s);
-    }
-}
-// k_rt's parameter block (pv_rt_push; pv_rt_pitchmap_push's stretch reads the same fields)
-pv::RtParams rt_params(const pv_rt* rt, const float* in, long long ldi, int nframes, float* out, long long ldo,
+pv::RtParams pvhost::rt_params(const pv_rt* rt, const float* in, long long ldi, int nframes, float* out, long long ldo,
                        pv_float2* spec, long long ld_spec) {
     const pv_handle* h = rt->h;
     pv::RtParams p{};
@@ -80,6 +50,43 @@ pv::RtParams rt_params(const pv_rt* rt, const float* in, long long ldi, int nfra
     p.q_pow2 = h->q_pow2;
     p.inv_q = h->inv_q;
     return p;
+}
+namespace {
+// the captured callback; the stream stays for the next capture
+void rt_release_graph(pv_rt* rt) {
+    if (rt->exec) (void)hipGraphExecDestroy(rt->exec);
+    if (rt->graph) (void)hipGraphDestroy(rt->graph);
+    rt->exec = nullptr;
+    rt->graph = nullptr;
+    rt->h_in.reset();
+    rt->h_out.reset();
+    rt->d_in.reset();
+    rt->d_out.reset();
+    rt->h_ratio.reset();
+    rt->d_ratio.reset();
+    rt->m_ratio = nullptr;
+    rt->h_gain.reset();
+    rt->d_gain.reset();
+    rt->m_gain = nullptr;
+    rt->g_nframes = 0;
+    rt->g_kind = pv_rt::kPush;
+}
+// samples per frame a callback emits: hop once pv_rt_pitch_reserve, pv_rt_pitchmap_reserve or
+// pv_rt_harmonizer_reserve has succeeded, else out hop
+int rt_out_hop(const pv_rt* rt) { return rt->callback != pv_rt::kPush ? rt->h->hop : rt->h->hs; }
+// what a callback runs: the push of the later successful reserve, else pv_rt_push (ratio: the
+// pitch map's [channels][nframes] ratios, or the harmoniser's [channels][voices][nframes] beside
+// its gains; the harmoniser's callback emits the mix)
+pv_status rt_callback_push(pv_rt* rt, const float* in, long long ldi, int nframes, const float* ratio,
+                           const float* gain, float* out, long long ldo, hipStream_t s) {
+    switch (rt->callback) {
+        case pv_rt::kHarmonPush:
+            return pv_rt_harmonizer_push(rt, in, ldi, nframes, ratio, gain, nframes, out, ldo, nullptr, 0, nullptr, 0, s);
+        case pv_rt::kPitchmapPush:
+            return pv_rt_pitchmap_push(rt, in, ldi, nframes, ratio, nframes, out, ldo, nullptr, 0, s);
+        case pv_rt::kPitchPush: return pv_rt_pitch_push(rt, in, ldi, nframes, out, ldo, nullptr, 0, s);
+        default: return pv_rt_push(rt, in, ldi, nframes, out, ldo, nullptr, 0, s);
+    }
 }
 // the real-time pitch map's stream state, zeroed (a stream's start)
 pv_status rt_pitchmap_zero(pv_rt* rt, hipStream_t s) {
@@ -126,7 +133,11 @@ pv_status pv_rt_reset(pv_rt* rt, void* stream) {
     PV_HIP(hipMemsetAsync(rt->d_M.p, 0, sizeof(int) * C * BP, s));
     PV_HIP(hipMemsetAsync(rt->d_tcount.p, 0, sizeof(unsigned) * C, s));
     if (rt->d_prow) PV_HIP(hipMemsetAsync(rt->d_prow.p, 0, sizeof(float) * C * (size_t)rt->ld_prow, s));
-    if (rt->pmap_on) return rt_pitchmap_zero(rt, s);
+    if (rt->pmap_on) {
+        pv_status st = rt_pitchmap_zero(rt, s);
+        if (st != PV_OK) return st;
+    }
+    if (rt->harm_on) return rt_harmon_zero(rt, s);
     return PV_OK;
 }
 
@@ -335,7 +346,7 @@ pv_status pv_rt_pitchmap_reserve(pv_rt* rt, int quality, int max_nframes, float 
     rt->pmap_rmax = ratio_max;
     if ((st = rt_pitchmap_zero(rt, nullptr)) != PV_OK || hipDeviceSynchronize() != hipSuccess) {
         rt->pmap_on = 0;
-        rt->callback = rt->pitch_on ? pv_rt::kPitchPush : pv_rt::kPush;
+        rt->callback = rt->harm_on ? pv_rt::kHarmonPush : rt->pitch_on ? pv_rt::kPitchPush : pv_rt::kPush;
         return st != PV_OK ? st : fail(PV_ERR_HIP, f + ": zeroing the stream state");
     }
     rt->pmap_on = 1;
@@ -403,7 +414,8 @@ pv_status pv_rt_pitchmap_push(pv_rt* rt, const float* in, long long ldi, int nfr
 
 pv_status pv_rt_pitchmap_host_ratios(pv_rt* rt, float** host_ratio) {
     if (!rt || !rt->exec) return fail(PV_ERR_ARG, "no captured callback (pv_rt_capture)");
-    if (!rt->h_ratio) return fail(PV_ERR_ARG, "pv_rt_pitchmap_host_ratios: the captured callback is not pv_rt_pitchmap_push");
+    if (rt->g_kind != pv_rt::kPitchmapPush)
+        return fail(PV_ERR_ARG, "pv_rt_pitchmap_host_ratios: the captured callback is not pv_rt_pitchmap_push");
     if (!host_ratio) return fail(PV_ERR_ARG, "null argument");
     *host_ratio = rt->h_ratio;
     return PV_OK;
@@ -417,6 +429,8 @@ pv_status pv_rt_capture(pv_rt* rt, int nframes) {
         return fail(PV_ERR_ARG, "pv_rt_capture: nframes > max_nframes of pv_rt_pitch_reserve");
     if (rt->callback == pv_rt::kPitchmapPush && nframes > rt->pmap_max)
         return fail(PV_ERR_ARG, "pv_rt_capture: nframes > max_nframes of pv_rt_pitchmap_reserve");
+    if (rt->callback == pv_rt::kHarmonPush && nframes > rt->harm_max)
+        return fail(PV_ERR_ARG, "pv_rt_capture: nframes > max_nframes of pv_rt_harmonizer_reserve");
     pv_handle* h = rt->h;
     DeviceGuard g(h->cfg.device);
     rt_release_graph(rt);
@@ -425,11 +439,14 @@ pv_status pv_rt_capture(pv_rt* rt, int nframes) {
     const size_t ni = (size_t)nframes * h->hop, no = (size_t)nframes * rt_out_hop(rt);
     // pinned, device-mapped host buffers: the captured kernel reads the callback's input
     // and writes its output in place over the bus (zero-copy: the graph is one kernel
-    // node, two after pv_rt_pitch_reserve or pv_rt_pitchmap_reserve, no copy nodes); if the runtime
-    // cannot map them, the graph copies H2D / D2H around the kernels instead.  The pitch map's
-    // ratios are a third such buffer, [channels][nframes], filled with 1.
-    const bool with_ratio = rt->callback == pv_rt::kPitchmapPush;
-    const size_t nr = with_ratio ? (size_t)nframes : 0;
+    // node, two after pv_rt_pitch_reserve, pv_rt_pitchmap_reserve or pv_rt_harmonizer_reserve, no
+    // copy nodes); if the runtime cannot map them, the graph copies H2D / D2H around the kernels
+    // instead.  The pitch map's ratios are a third such buffer, [channels][nframes], filled with 1;
+    // the harmoniser's ratios, [channels][voices][nframes], filled with 1, and its gains, a fourth
+    // of the same shape, filled with 1 / voices.
+    const bool with_gain = rt->callback == pv_rt::kHarmonPush;
+    const bool with_ratio = with_gain || rt->callback == pv_rt::kPitchmapPush;
+    const size_t nr = with_gain ? (size_t)rt->harm_voices * (size_t)nframes : with_ratio ? (size_t)nframes : 0;
     PV_HIP(rt->h_in.alloc(C * ni));
     PV_HIP(rt->h_out.alloc(C * no));
     std::memset(rt->h_in, 0, sizeof(float) * C * ni);
@@ -438,16 +455,23 @@ pv_status pv_rt_capture(pv_rt* rt, int nframes) {
         PV_HIP(rt->h_ratio.alloc(C * nr));
         std::fill(rt->h_ratio.p, rt->h_ratio.p + C * nr, 1.0f);
     }
-    float *m_in = nullptr, *m_out = nullptr, *m_ratio = nullptr;
+    if (with_gain) {
+        PV_HIP(rt->h_gain.alloc(C * nr));
+        std::fill(rt->h_gain.p, rt->h_gain.p + C * nr, 1.0f / (float)rt->harm_voices);
+    }
+    float *m_in = nullptr, *m_out = nullptr, *m_ratio = nullptr, *m_gain = nullptr;
     bool zero_copy = hipHostGetDevicePointer((void**)&m_in, rt->h_in, 0) == hipSuccess &&
                      hipHostGetDevicePointer((void**)&m_out, rt->h_out, 0) == hipSuccess && m_in && m_out;
     if (zero_copy && with_ratio)
         zero_copy = hipHostGetDevicePointer((void**)&m_ratio, rt->h_ratio, 0) == hipSuccess && m_ratio;
+    if (zero_copy && with_gain)
+        zero_copy = hipHostGetDevicePointer((void**)&m_gain, rt->h_gain, 0) == hipSuccess && m_gain;
     if (!zero_copy) {
         (void)hipGetLastError();
         PV_HIP(rt->d_in.alloc(C * ni));
         PV_HIP(rt->d_out.alloc(C * no));
         if (with_ratio) PV_HIP(rt->d_ratio.alloc(C * nr));
+        if (with_gain) PV_HIP(rt->d_gain.alloc(C * nr));
     }
     hipStream_t s = rt->g_stream;
     hipGraph_t graph = nullptr;
@@ -456,15 +480,17 @@ pv_status pv_rt_capture(pv_rt* rt, int nframes) {
         PV_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
         pv_status st = PV_OK;
         if (zero_copy) {
-            st = rt_callback_push(rt, m_in, (long long)ni, nframes, m_ratio, m_out, (long long)no, s);
+            st = rt_callback_push(rt, m_in, (long long)ni, nframes, m_ratio, m_gain, m_out, (long long)no, s);
         } else {
             if (hipMemcpyAsync(rt->d_in, rt->h_in, sizeof(float) * C * ni, hipMemcpyHostToDevice, s) != hipSuccess ||
                 (with_ratio && hipMemcpyAsync(rt->d_ratio, rt->h_ratio, sizeof(float) * C * nr, hipMemcpyHostToDevice,
-                                              s) != hipSuccess))
+                                              s) != hipSuccess) ||
+                (with_gain && hipMemcpyAsync(rt->d_gain, rt->h_gain, sizeof(float) * C * nr, hipMemcpyHostToDevice,
+                                             s) != hipSuccess))
                 st = fail(PV_ERR_HIP, "pv_rt_capture: H2D capture failed");
             if (st == PV_OK)
-                st = rt_callback_push(rt, rt->d_in, (long long)ni, nframes, rt->d_ratio, rt->d_out, (long long)no,
-                                      s);
+                st = rt_callback_push(rt, rt->d_in, (long long)ni, nframes, rt->d_ratio, rt->d_gain, rt->d_out,
+                                      (long long)no, s);
             if (st == PV_OK &&
                 hipMemcpyAsync(rt->h_out, rt->d_out, sizeof(float) * C * no, hipMemcpyDeviceToHost, s) != hipSuccess)
                 st = fail(PV_ERR_HIP, "pv_rt_capture: D2H capture failed");
@@ -479,9 +505,11 @@ pv_status pv_rt_capture(pv_rt* rt, int nframes) {
     rt->graph = graph;
     PV_HIP(hipGraphInstantiate(&rt->exec, graph, nullptr, nullptr, 0));
     rt->g_nframes = nframes;
+    rt->g_kind = rt->callback;
     rt->m_in = zero_copy ? m_in : nullptr;
     rt->m_out = zero_copy ? m_out : nullptr;
     rt->m_ratio = zero_copy ? m_ratio : nullptr;
+    rt->m_gain = zero_copy ? m_gain : nullptr;
     const char* lv = std::getenv("PV_RT_LAUNCH");
     rt->direct = (zero_copy && lv && std::string(lv) == "direct") ? 1 : 0;
     return PV_OK;
@@ -502,8 +530,8 @@ pv_status pv_rt_callback(pv_rt* rt, const float* in, float* out) {
     const size_t ni = (size_t)rt->g_nframes * h->hop, no = (size_t)rt->g_nframes * rt_out_hop(rt);
     if (in && in != rt->h_in) std::memcpy(rt->h_in, in, sizeof(float) * C * ni);  // main.cpp:49
     if (rt->direct) {
-        pv_status st = rt_callback_push(rt, rt->m_in, (long long)ni, rt->g_nframes, rt->m_ratio, rt->m_out,
-                                        (long long)no, rt->g_stream);
+        pv_status st = rt_callback_push(rt, rt->m_in, (long long)ni, rt->g_nframes, rt->m_ratio, rt->m_gain,
+                                        rt->m_out, (long long)no, rt->g_stream);
         if (st != PV_OK) return st;
     } else {
         PV_HIP(hipGraphLaunch(rt->exec, rt->g_stream));

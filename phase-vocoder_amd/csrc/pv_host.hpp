@@ -33,13 +33,14 @@ pv_status fail(pv_status s, const std::string& msg);
 
 // kernel ids of the per-launch profile and their names (pv_profile_read), index for index
 enum { KA, KRS, KC, KS, KSEAM, KCA, KRT, KF, KSL, KENV, KSF, KRES, KRTR, KSW, KON, KPK, KRST, KSR, KMS, KMC, KSM,
-       KVR, KRD, KPT, KRTM, KRTV, kNumKernels };
+       KVR, KRD, KPT, KRTM, KRTV, KRTH, KRTHR, kNumKernels };
 inline constexpr const char* kKernelNames[] = {"analysis", "runsum", "carry", "synthesis", "seam",
                                                "compat_analysis", "rt", "fused", "synthesis_locked",
                                                "envelope", "synthesis_formant", "resample", "rt_resample",
                                                "synthesis_warp", "onset", "pick", "reset", "synthesis_reset",
                                                "map_sum", "map_carry", "synthesis_map", "var_resample",
-                                               "resident", "pitch", "rt_map", "rt_varresample"};
+                                               "resident", "pitch", "rt_map", "rt_varresample",
+                                               "rt_hmap", "rt_hresample"};
 static_assert(sizeof(kKernelNames) / sizeof(kKernelNames[0]) == kNumKernels, "one name per kernel id");
 
 // Move-only owner of one hipMalloc (Pinned: hipHostMalloc, device-mapped) allocation.  Converts
@@ -224,15 +225,30 @@ struct pv_rt {
     pvhost::DevBuf<pv::RtMapState> d_mstate;
     pvhost::DevBuf<long long> d_mring;
     pvhost::DevBuf<float> d_mrow;
+    // pv_rt_harmonizer_reserve: the real-time harmoniser's voices, preset, ratio
+    // range and plan (the pitch map's, per voice), and its stream state: per channel d_hprev
+    // [bins_pad] the last analysed row (the input history is d_hist); per (channel, voice) d_hphi
+    // [bins_pad], d_hola [N] the overlap accumulator, d_hstate, d_hring [ring_cap] {step, gain},
+    // d_hrow [row_len], d_hgprev the last emitted gain; d_hwin: the window table
+    int harm_on = 0, harm_voices = 0, harm_quality = 0, harm_max = 0;
+    float harm_rmin = 1.0f, harm_rmax = 1.0f;
+    pvtab::RtPitchmapPlan harm_plan{};
+    pvhost::DevBuf<float2> d_hprev, d_hwin;
+    pvhost::DevBuf<unsigned> d_hphi;
+    pvhost::DevBuf<float> d_hola, d_hrow;
+    pvhost::DevBuf<pv::RtMapState> d_hstate;
+    pvhost::DevBuf<pv::RtHStep> d_hring;
+    pvhost::DevBuf<pv::RtHGain> d_hgprev;
     // what pv_rt_capture records: the later successful reserve decides
-    enum { kPush = 0, kPitchPush = 1, kPitchmapPush = 2 };
+    enum { kPush = 0, kPitchPush = 1, kPitchmapPush = 2, kHarmonPush = 3 };
     int callback = kPush;
-    // captured callback (h_ratio / d_ratio / m_ratio: the ratios of a captured pv_rt_pitchmap_push,
-    // [channels][g_nframes])
-    int g_nframes = 0;
-    pvhost::DevBuf<float, true> h_in, h_out, h_ratio;
-    pvhost::DevBuf<float> d_in, d_out, d_ratio;
-    float* m_ratio = nullptr;
+    // captured callback: g_kind is the `callback` it recorded.  h_ratio / d_ratio / m_ratio: the
+    // ratios of a captured pv_rt_pitchmap_push, [channels][g_nframes], or of a captured
+    // pv_rt_harmonizer_push, [channels][voices][g_nframes], whose gains are h_gain / d_gain / m_gain
+    int g_nframes = 0, g_kind = kPush;
+    pvhost::DevBuf<float, true> h_in, h_out, h_ratio, h_gain;
+    pvhost::DevBuf<float> d_in, d_out, d_ratio, d_gain;
+    float *m_ratio = nullptr, *m_gain = nullptr;
     hipStream_t g_stream = nullptr;
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
@@ -372,6 +388,13 @@ pv_status do_seam(pv_handle* h, int C, int frames, const float* ola_in, long lon
 pv_status own_spectrum(pv_handle* h, const char* fn, hipStream_t s, pv_float2** spec, long long* ld_spec);
 // own_rows: allocate the handle's envelope rows (a harmoniser's voices k > 0 read voice 0's)
 pv_status set_formant(pv_handle* h, int order, bool own_rows);
+
+// ---- real-time mode (pv_api_rt.cpp): k_rt's parameter block (pv_rt_push; the stretches of
+// pv_rt_pitchmap_push and pv_rt_harmonizer_push read the same fields)
+pv::RtParams rt_params(const pv_rt* rt, const float* in, long long ldi, int nframes, float* out, long long ldo,
+                       pv_float2* spec, long long ld_spec);
+// ---- real-time harmoniser (pv_api_rt_harmon.cpp): its stream state, zeroed (a stream's start)
+pv_status rt_harmon_zero(pv_rt* rt, hipStream_t s);
 
 // ---- transient phase reset (pv_api_transient.cpp)
 // the handle's transient buffers exist, or are allocated now (refused while s is being captured)

@@ -402,6 +402,58 @@ struct RtVarParams {
     double rolloff, Z;                 // the preset's (Sq_b and W_b are computed here, in fp64)
 };
 
+// real-time harmoniser (pv_rt_harmon.hip): V voices of the real-time pitch map per
+// channel, two launches per callback.  Per (channel, voice) — index c V + v — the stream keeps what
+// the pitch map keeps per channel (RtMapState, Phi, the overlap accumulator, the scratch row), a
+// ring of {step, gain} of the blocks not yet emitted, and the gain of the last emitted block; per
+// channel the input history and the last analysed row.
+constexpr int kRtHarmonMaxVoices = 8;
+struct RtHStep {
+    long long d;     // the block's step, 2^-32 samples
+    float gain;      // the block's gain (a NaN stored as 0)
+    int pad;
+};
+struct RtHGain {
+    float g;         // gain of the last emitted block
+    int have;        // 0: no block emitted yet (block 0 ramps from its own gain)
+};
+// k_rt_hmap: RtMapParams with a voice dimension (rt.ola is not used: the accumulators are ola)
+struct RtHMapParams {
+    RtParams rt;
+    int voices;
+    const float* ratio;                // [C][V][nframes] (row stride ld_ctl), or nullptr: 1
+    const float* gain;                 // [C][V][nframes] (row stride ld_ctl), or nullptr: 1 / V
+    long long ld_ctl;
+    float ratio_min, ratio_max;
+    float2* prev;                      // [C][bins_pad] {mag, bits of P} of the last analysed row
+    unsigned* phi;                     // [C][V][bins_pad] Phi, fractions of a turn
+    float* ola;                        // [C][V][N] overlap accumulators
+    RtMapState* st;                    // [C][V]
+    RtHStep* ring;                     // [C][V][ring_cap]
+    int ring_cap;                      // >= G + the largest nframes
+    float* row;                        // [C][V][ld_row]
+    long long ld_row;
+    int K;
+};
+// k_rt_hresample: RtVarParams with a voice dimension and the mix
+struct RtHVarParams {
+    float* row;
+    long long ld_row;
+    int K;
+    float* mix;                        // [C][nframes * hop] (row stride ldo)
+    long long ldo;
+    float* voices_out;                 // [V][C][nframes * hop] (row stride ld_voice), or nullptr
+    long long ld_voice;
+    RtMapState* st;
+    RtHStep* ring;
+    int ring_cap;
+    RtHGain* gprev;                    // [C][V]
+    const float2* win;                 // the window table of pv_varresample.hpp
+    float win_scale;
+    int channels, voices, nframes, hop, G;
+    double rolloff, Z;                 // the preset's (Sq_b and W_b are computed here, in fp64)
+};
+
 // harmoniser mix: dst[c][i] = sum_k gain[k] * src[k][c][i]
 struct MixParams {
     const float* src;
@@ -476,6 +528,11 @@ hipError_t launch_rt_resample(const RtResampleParams& p, hipStream_t s);
 bool rt_map_kernel(int L);
 hipError_t launch_rt_map(int L, int lock, const RtMapParams& p, hipStream_t s);
 hipError_t launch_rt_varresample(const RtVarParams& p, hipStream_t s);
+// real-time harmoniser (pv_rt_harmon.hip): the most voices k_rt_hmap takes at this size (0: no
+// kernel), and the launches
+int rt_hmap_max_voices(int L);
+hipError_t launch_rt_hmap(int L, int lock, const RtHMapParams& p, hipStream_t s);
+hipError_t launch_rt_hresample(const RtHVarParams& p, hipStream_t s);
 hipError_t launch_window_gain(const float* win, float* dwin, float* gain, int n, hipStream_t s);
 hipError_t launch_overlap_test(const float* in, const float* win, const float* back, float* out,
                                int n, int hop, hipStream_t s);

@@ -444,6 +444,10 @@ void var_window_table(int quality, int n, int len, std::vector<float>& tab) {
 
 // The real-time pitch map's latency and buffer sizes (integers; the steps are exact: an fp32 at or
 // above 1/4 is a multiple of 2^-26)
+int rt_harmonizer_max_voices(int n_samps) {
+    return (n_samps == 256 || n_samps == 512 || n_samps == 1024) ? 8 : (n_samps == 2048) ? 4 : 0;
+}
+
 bool rt_pitchmap_plan(int hop, int quality, float ratio_min, float ratio_max, int max_nframes, RtPitchmapPlan* out) {
     if (hop < 1 || max_nframes < 1 || (quality != 0 && quality != 1)) return false;
     if (!(ratio_min >= 0.25f) || !(ratio_max <= 4.0f) || !(ratio_min <= ratio_max)) return false;

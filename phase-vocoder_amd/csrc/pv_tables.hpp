@@ -139,6 +139,10 @@ struct RtPitchmapPlan {
     long long row_len, ring_cap;
 };
 bool rt_pitchmap_plan(int hop, int quality, float ratio_min, float ratio_max, int max_nframes, RtPitchmapPlan* out);
+// ---- real-time harmoniser (pv_rt_harmonizer_*): the most voices per channel at
+// this n_samps (a wave per voice in one workgroup, its LDS the bound: 8, 8, 8, 4 for 256 .. 2048), 0
+// where there is no kernel.  Every voice plans as rt_pitchmap_plan.
+int rt_harmonizer_max_voices(int n_samps);
 
 // ---- pitch correction (pv_pitch_correct_plan): track [frames] {f0, strength}
 // -> ratio [n], one per output frame (pos: its analysis position, nullptr: u); false on a bad

@@ -196,6 +196,18 @@ def lib():
     L.pv_rt_pitchmap_push.restype = i
     L.pv_rt_pitchmap_host_ratios.argtypes = [vp, fpp]
     L.pv_rt_pitchmap_host_ratios.restype = i
+    L.pv_rt_harmonizer_max_voices.argtypes = [i]
+    L.pv_rt_harmonizer_max_voices.restype = i
+    L.pv_rt_harmonizer_reserve.argtypes = [vp, i, i, i, f, f]
+    L.pv_rt_harmonizer_reserve.restype = i
+    L.pv_rt_harmonizer_voices.argtypes = [vp]
+    L.pv_rt_harmonizer_voices.restype = i
+    L.pv_rt_harmonizer_latency.argtypes = [vp]
+    L.pv_rt_harmonizer_latency.restype = i
+    L.pv_rt_harmonizer_push.argtypes = [vp, vp, ll, i, vp, vp, ll, vp, ll, vp, ll, vp, ll, vp]
+    L.pv_rt_harmonizer_push.restype = i
+    L.pv_rt_harmonizer_host_controls.argtypes = [vp, fpp, fpp]
+    L.pv_rt_harmonizer_host_controls.restype = i
     L.pv_fft_c2c.argtypes = [vp, vp, i, i, i, vp]
     L.pv_fft_c2c.restype = i
     L.pv_harmonizer_create.argtypes = [ctypes.POINTER(pv_config), ctypes.POINTER(ctypes.c_float), i,
